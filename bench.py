@@ -16,8 +16,11 @@ HIP streams, --micro) through the whole hot path with the decoder outputs alread
 Multi-GPU (--gpus N): BASELINE config 3 -- the 8 views of the batch sharded 8 / N per GPU (strong scaling), the 60 M-float
 gradient exchange of the decoder's parameter set inside the step; --weak keeps 8 views per rank.
 
-Prints ONE JSON line (rank 0).  Per-ABI-call durations come from HIP events recorded on the launch
-stream inside the timed region; `roofline` describes the longest one.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline (`value`,
+`ms_per_step`, the timing windows and the configuration); --dump-outputs DIR also writes what the last timed step
+computed.  --full adds everything else measured around it: per-ABI-call durations from an eager instrumented pass after
+the timed region (`roofline` describes the longest call), intersection counts, the exchange alone (N > 1), the
+overlapped / weak variants (N > 1), the secondary workloads, the CPU baseline and the parity record.
 """
 import argparse
 import json
@@ -166,17 +169,22 @@ def compact_line(res):
     return out
 
 
-def emit(obj):
-    """Full record -> gpurun_out/bench_detail.json and stderr; the compact one-line record -> stdout."""
-    full = _clean(obj)
-    try:
-        os.makedirs(os.path.dirname(DETAIL_PATH), exist_ok=True)
-        with open(DETAIL_PATH, "w") as f:
-            json.dump(full, f, allow_nan=False, indent=1)
-    except OSError as e:
-        print(f"bench.py: could not write {DETAIL_PATH}: {e}", file=sys.stderr)
-    print("bench.py detail: " + json.dumps(full, allow_nan=False), file=sys.stderr, flush=True)
-    text = json.dumps(compact_line(obj), allow_nan=False, separators=(",", ":"))
+def emit(obj, detail=True):
+    """Full record -> DETAIL_PATH and stderr; the compact one-line record -> stdout.  detail=False (a plain run): the
+    one-line record alone."""
+    line = compact_line(obj)
+    if detail:
+        full = _clean(obj)
+        try:
+            os.makedirs(os.path.dirname(DETAIL_PATH), exist_ok=True)
+            with open(DETAIL_PATH, "w") as f:
+                json.dump(full, f, allow_nan=False, indent=1)
+        except OSError as e:
+            print(f"bench.py: could not write {DETAIL_PATH}: {e}", file=sys.stderr)
+        print("bench.py detail: " + json.dumps(full, allow_nan=False), file=sys.stderr, flush=True)
+    else:
+        line.pop("detail", None)
+    text = json.dumps(line, allow_nan=False, separators=(",", ":"))
     assert len(text) < LINE_LIMIT, len(text)
     line = (text + "\n").encode()
     if _REAL_STDOUT is None:
@@ -306,7 +314,11 @@ def step(t, cfg, world):
     def render_and_backward(mb, p):
         # loss == (rgb - target).abs().mean() (loss/__init__.py:411), evaluated in the raster epilogue and
         # back-propagated by the raster backward itself (losses.l1_image is the stand-alone form of the same op)
-        loss = render_gs.render_batch(mb["K"], mb["Rt"], p, cfg["height"], cfg["width"], l1_target=mb["target"])[3]
+        out = render_gs.render_batch(mb["K"], mb["Rt"], p, cfg["height"], cfg["width"], l1_target=mb["target"])
+        if cfg.get("keep_outputs"):   # --dump-outputs: rgb, alpha, depth, loss stay referenced past the step
+            mb["_out"] = out
+        loss = out[3]
+        del out
         loss.backward()
         return loss
 
@@ -336,6 +348,42 @@ def step(t, cfg, world):
         torch.add(grads[0], grads[1]) if len(grads) == 2 else torch.stack(grads).sum(0))
     t["albedo"].grad = t["_albedo_grad"]
     return loss
+
+
+DUMP_SAMPLE = 1 << 20   # elements written of an output larger than this
+
+
+def dump_outputs(t, out_dir):
+    """--dump-outputs: what the last timed step computed, as out_dir/<name>.npy (float32) -- the per-micro-batch L1
+    losses, the rendered rgb / alpha / depth of all views and the gradients of the step's leaves (the shared albedo's
+    summed over the micro-batches).  An output of more than DUMP_SAMPLE elements is written as the elements at
+    DUMP_SAMPLE flat indices drawn (sorted, with replacement) from a generator seeded by the output's name: the same
+    positions in every run, so two builds compare element for element.  About 30 MB in all."""
+    import zlib
+
+    import numpy as np
+
+    micro = t["micro"]
+    outs = {"loss": torch.stack([mb["_out"][3].detach().reshape(()) for mb in micro])}
+    for i, name in enumerate(("rgb", "alpha", "depth")):
+        outs[name] = torch.cat([mb["_out"][i].detach() for mb in micro])
+    for k in ("f_vn", "f_vc", "postex", "tn"):
+        assert all(mb[k].grad is not None for mb in micro), f"no gradient reached {k}"
+        outs["grad_" + k] = torch.cat([mb[k].grad for mb in micro])
+    outs["grad_albedo"] = t["albedo"].grad
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, x in outs.items():
+        x = x.detach()
+        if x.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(x.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            x = x.reshape(-1)[idx.to(x.device)]
+        a = np.ascontiguousarray(x.float().cpu().numpy())
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    print(f"bench.py: wrote {len(outs)} outputs of the last timed step ({total / 2**20:.1f} MiB) to {out_dir}",
+          file=sys.stderr)
 
 
 def _split(n, parts):
@@ -977,8 +1025,15 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1,
                     help="N > 1 without torchrun: this script re-executes itself as N ranks (one per GPU) under "
                          "torch.distributed.run; under torchrun WORLD_SIZE must equal N.  Never a silent N = 1")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-call durations and rooflines from an instrumented pass, intersection "
+                         "counts, the exchange alone and the overlapped / weak variants (N > 1), the secondary workloads, "
+                         "the CPU baseline and the parity record, with the full record in the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rgca: write what the last timed step computed as DIR/<name>.npy (float32; outputs of more than "
+                         "2^20 elements as a fixed, seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--views", type=int, default=None,
                     help="views per GPU and step.  Default: BASELINE config 2's batch of 8 views, sharded 8 / N per GPU for "
@@ -1026,15 +1081,20 @@ def parse_args(argv=None):
                     help="rgca: run the EWA projection and its backward as kernels of their own (gol_project_fwd / bwd inside "
                          "gol_render_fwd / bwd, rounds 1-3) instead of inside the shading kernels (gol_shade_project_fwd / bwd)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="rgca, N = 1: skip the secondary workloads (one camera per GPU, e2e at 1 M Gaussians, MVP config 5, "
-                         "URHand config 4, the coherent / smooth env-map case) that the default line carries under `secondary`")
+                    help="rgca, N = 1, --full: skip the secondary workloads (one camera per GPU, e2e at 1 M Gaussians, MVP "
+                         "config 5, URHand config 4, the coherent / smooth env-map case) that the line carries under `secondary`")
     ap.add_argument("--fused-tail", action="store_true", default=True,
                     help="e2e: light-contracted last decoder layers on gol_tail_conv_* (default)")
     ap.add_argument("--unfused-tail", dest="fused_tail", action="store_false",
                     help="e2e: last decoder layers as PyTorch/MIOpen transposed convs + bias adds (the reference's structure)")
     ap.add_argument("--no-ssim", action="store_true", help="e2e: L1 loss only (default: 10*L1 + 0.2*(1-SSIM))")
     ap.add_argument("--segments", action="store_true", help="e2e: also report per-segment times (adds a sync per step)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.workload != "rgca" or args.stub):
+        ap.error("--dump-outputs writes the outputs of the rgca step: not with --workload other than rgca or --stub")
+    return args
 
 
 CONFIG2_VIEWS = CFG["views_per_gpu"]   # BASELINE configs[1] / [2]: ONE batch of 8 views (config 3 = the same batch, 8 / N per GPU)
@@ -1051,12 +1111,14 @@ def plan_views(args, world):
     return CONFIG2_VIEWS, "weak", CFG["workload"]
 
 
-def run_rgca(args, D, views, scaling, workload, overlap, micro=None, extras=True):
+def run_rgca(args, D, views, scaling, workload, overlap, micro=None, extras=True, dump=None):
     """Warm up, capture and time the rgca step for `views` views per rank; returns the result dict (rank 0; None on the
-    other ranks).  overlap: exchange mode for N > 1 (see run_step).  extras: intersection counts, per-call HBM table."""
+    other ranks).  overlap: exchange mode for N > 1 (see run_step).  extras: intersection counts, per-call HBM table.
+    dump: directory for the outputs of the last timed step (rank 0, see dump_outputs).  args.full: also the exchange
+    alone and the per-call durations of an instrumented eager pass after the timed region."""
     cfg = dict(CFG, workload=workload, views_per_gpu=views, coherent_uv=bool(args.coherent_uv),
                smooth_normals=bool(args.smooth_normals), fused_projection=not args.unfused_projection,
-               env_per_view=bool(getattr(args, "env_per_view", False)))
+               env_per_view=bool(getattr(args, "env_per_view", False)), keep_outputs=bool(dump))
     # with the projection fused in, micro-batches of >= 4 views are joined once after their shading kernels (see step();
     # measured: 8 views 2803 -> 2855 views/s; 2 + 2 and 1 + 1 views are faster left alone, and so is the unfused path)
     cfg["align_micro_batches"] = (cfg["fused_projection"] and views // max(1, min(args.micro if micro is None else micro, views)) >= 4
@@ -1143,8 +1205,10 @@ def run_rgca(args, D, views, scaling, workload, overlap, micro=None, extras=True
     dt = time.perf_counter() - t0
     win_ms = [(marks[i].elapsed_time(marks[i + 1]) if on_gpu else 1e3 * (marks[i + 1] - marks[i])) / n
               for i, n in enumerate(plan)]
+    if dump and rank == 0:
+        dump_outputs(t, dump)
     exchange_ms = None
-    if exchanging and args.steps > 0:
+    if exchanging and args.steps > 0 and args.full:
         # the exchange alone, serial, right after the timed region (same buffers): what it costs when nothing hides it
         D.barrier()
         te = time.perf_counter()
@@ -1158,6 +1222,9 @@ def run_rgca(args, D, views, scaling, workload, overlap, micro=None, extras=True
         if graph is not None:
             splat.PLANNER.check_frozen()  # raises if a replayed render overflowed its intersection capacity
             splat.PLANNER.frozen = False
+    if on_gpu and not args.stub and not args.full:
+        splat.PLANNER.poll(block=True)  # raises if any step overflowed its intersection capacity
+    if on_gpu and not args.stub and args.full:
         # The timed region runs UN-instrumented (graph replays, or the eager composite calls an unmodified training loop
         # issues).  The per-call durations come from an eager, instrumented pass of the same K steps right after it (same
         # buffers; HIP events cannot bracket nodes inside a captured graph, and the per-stage calls the events need are not
@@ -1363,13 +1430,18 @@ def main():
     # the averaged gradients before the next forward); the overlapped variant (step k's exchange beside step k+1's
     # compute) is measured right after it and reported beside it, never as `value`
     overlap_only = bool(args.overlap_exchange) and not args.serial_exchange
-    res = run_rgca(args, D, views, scaling, workload, overlap=overlap_only)
+    res = run_rgca(args, D, views, scaling, workload, overlap=overlap_only, extras=args.full, dump=args.dump_outputs)
     if args.stub:
         if D.rank == 0:
-            emit(res)
+            emit(res, detail=args.full)
         D.shutdown()
         if D.rank == 0 and res.get("stub_gradients_averaged") is False:
             sys.exit(3)
+        return
+    if not args.full:   # a plain run: the headline alone
+        if D.rank == 0:
+            emit(res, detail=False)
+        D.shutdown()
         return
     _release()
     if multi and not overlap_only and not args.serial_exchange:

@@ -20,6 +20,8 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))   # tests/: npz_parts
+import npz_parts  # noqa: E402
 REF = "/root/reference/extensions"
 
 
@@ -74,8 +76,8 @@ def mvp():
     })
     print("w alpha range", float(L["sample0"][..., 3].min()), float(L["sample0"][..., 3].max()))
     path = os.path.join(HERE, "mvp_golden.npz")
-    np.savez_compressed(path, **{k: v.detach().cpu().numpy().astype(np.float32) for k, v in out.items()})
-    print("wrote", path, os.path.getsize(path))
+    parts = npz_parts.save(path, {k: v.detach().cpu().numpy().astype(np.float32) for k, v in out.items()})
+    print("wrote", len(parts), "parts of", path, sum(os.path.getsize(p) for p in parts))   # < 1 MiB each
 
 
 def raydirs():

@@ -36,6 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 for p in (ROOT, os.path.join(ROOT, "tests"), HERE):
     if p not in sys.path:
         sys.path.insert(0, p)
+import npz_parts  # noqa: E402
 import ref_stubs  # noqa: E402
 from oracle import cref, gsplat_module, refso  # noqa: E402
 
@@ -328,8 +329,8 @@ def raw_case():
     print("raw_point: alpha mean", float(preds["alpha"].mean()), "sigma min", float(preds["sigma"].min()), "max",
           float(preds["sigma"].max()), "rgb mean", float(preds["rgb"].mean()))
     path = os.path.join(HERE, "rgca_model_raw_golden.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes;", len(out), "arrays")
+    parts = npz_parts.save(path, out)   # parts of < 1 MiB each (tests/npz_parts.py)
+    print("wrote", len(parts), "parts of", path, sum(os.path.getsize(p) for p in parts), "bytes;", len(out), "arrays")
 
 
 def main():
@@ -435,8 +436,8 @@ def main():
     out["vis_env/compose/bg_term"] = (x00 - x01).numpy().copy()                    # (1 - ma) * bg
     out["vis_env/compose/mirror_term"] = x01.numpy().copy()                        # ma * mi
     path = os.path.join(HERE, "rgca_model_golden.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes;", len(out), "arrays")
+    parts = npz_parts.save(path, out)   # parts of < 1 MiB each (tests/npz_parts.py)
+    print("wrote", len(parts), "parts of", path, sum(os.path.getsize(p) for p in parts), "bytes;", len(out), "arrays")
     raw_case()
 
 

@@ -19,7 +19,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 pytestmark = pytest.mark.gpu
-SMALL = ["--views", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--grad-floats", "1000000"]
+# --full: the assertions read intersection counts and the exchange-alone time, which a plain run does not measure
+SMALL = ["--full", "--views", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--grad-floats", "1000000"]
 
 
 def _run(args, timeout=900):

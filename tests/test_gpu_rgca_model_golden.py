@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+import npz_parts
 import rgca_shaped as S
 from scenes import rel_l2
 
@@ -41,7 +42,7 @@ BAR_PER_GAUSSIAN, BAR_IMAGE, BAR_GRAD = 3e-5, 5e-5, 1e-4  # gradients: north_sta
 
 
 def _gold():
-    return np.load(GOLD_PATH)
+    return npz_parts.load(GOLD_PATH)
 
 
 def _t(a):
@@ -349,7 +350,7 @@ def test_raw_scene_point_lights_w_protocol(fused_tail, monkeypatch):
     monkeypatch.setenv("GOLIATH_FUSED_TAIL", "1" if fused_tail else "0")
     tag = "raw_point" + ("_fused_tail" if fused_tail else "")
 
-    G = np.load(RAW_PATH)
+    G = npz_parts.load(RAW_PATH)
     st = _stored(G, "raw_point")
     embs, geom = (t.detach().cuda().requires_grad_(True) for t in S.leaves(2, RAW_SEED, st))
     from goliath_amd import rgca

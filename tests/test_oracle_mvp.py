@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import npz_parts
 from oracle import cref
 from scenes import rel_l2
 
@@ -14,7 +15,7 @@ GDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def load(name):
-    z = np.load(os.path.join(GDIR, name))
+    z = npz_parts.load(os.path.join(GDIR, name))
     return {k: torch.from_numpy(z[k]) for k in z.files}
 
 

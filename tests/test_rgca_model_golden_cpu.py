@@ -15,6 +15,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import npz_parts
 import rgca_shaped as S
 from scenes import rel_l2
 
@@ -27,7 +28,7 @@ def _t(a):
 
 
 def test_fixture_has_every_key_of_the_reference_forward():
-    G = np.load(GOLD)
+    G = npz_parts.load(GOLD)
     for tag, extra in (("train_point", ("color_rand", "cos_weight", "learn_blur_weights")), ("eval_env", ())):
         for k in S.OUTPUT_KEYS + tuple(extra):
             assert f"{tag}/out/{k}" in G.files, (tag, k)
@@ -53,7 +54,7 @@ def test_stand_in_regenerates_and_the_shading_oracle_reproduces_the_reference_de
     # generated with the weight-norm denominator in fp64 (see make_rgca_model_golden.py), the GPU's tree reduction agrees with
     # that to 3e-7 -- so on the CPU the stand-in's layers get the same fp64 denominator here
     monkeypatch.setattr(D, "_wn", lambda v, g: v * (g / v.double().pow(2).sum().sqrt().to(v.dtype)))
-    G = np.load(GOLD)
+    G = npz_parts.load(GOLD)
     B = 2
     st = {k.split("/stored/")[1]: G[k] for k in G.files if k.startswith(f"{tag}/stored/")}
     embs, geom = S.leaves(B, seed, st)

@@ -7,7 +7,7 @@ for r in $(seq $REPS); do
   i=0
   for a in "$@"; do
     i=$((i+1))
-    python bench.py --no-cpu-baseline --no-secondary --steps 20 --warmup 3 $a 2>$OUT/err_$i.txt | python -c "
+    python bench.py --full --no-cpu-baseline --no-secondary --steps 20 --warmup 3 $a 2>$OUT/err_$i.txt | python -c "
 import json,sys
 l=sys.stdin.readline()
 try:

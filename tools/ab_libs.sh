@@ -8,7 +8,7 @@ OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 run() {  # arm lib mode args...
   local arm=$1 lib=$2 mode=$3; shift 3
   if [ -n "$lib" ]; then export GOLIATH_HIP_LIB=$PWD/$lib; else unset GOLIATH_HIP_LIB; fi
-  python bench.py --no-cpu-baseline --no-secondary --steps 20 --warmup 3 "$@" 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-secondary --steps 20 --warmup 3 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 k=d['kernels_ms_per_call']

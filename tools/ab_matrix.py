@@ -30,7 +30,7 @@ def main():
         for v in views:
             modes = [("eager1", ["--micro", "1", "--no-graph"])] + ([("graph", [])] if graph else [])
             for mode, margs in modes:
-                cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--views", str(v), "--no-cpu-baseline",
+                cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--views", str(v), "--no-cpu-baseline",
                        "--no-secondary", "--steps", "20", "--warmup", "3"] + margs + extra
                 r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
                 lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -10,12 +10,13 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import npz_parts
 import rgca_shaped as S
 from goliath_amd import decoder as D, shade
 from oracle import shade_ref
 
 D._wn = lambda v, g: v * (g / v.double().pow(2).sum().sqrt().to(v.dtype))
-G = np.load(os.path.join(ROOT, "tests", "golden", "rgca_model_golden.npz"))
+G = npz_parts.load(os.path.join(ROOT, "tests", "golden", "rgca_model_golden.npz"))
 t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
 tag, B, seed = "eval_env", 2, 100
 st = {k.split("/stored/")[1]: G[k] for k in G.files if k.startswith(f"{tag}/stored/")}

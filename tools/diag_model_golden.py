@@ -11,10 +11,11 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import npz_parts
 import rgca_shaped as S
 from scenes import rel_l2
 
-G = np.load(os.path.join(ROOT, "tests", "golden", "rgca_model_golden.npz"))
+G = npz_parts.load(os.path.join(ROOT, "tests", "golden", "rgca_model_golden.npz"))
 embs, geom = S.leaves(2, 0)
 m = S.ShapedAutoEncoder(embs, geom, 0)
 dec = m.decoder.eval()

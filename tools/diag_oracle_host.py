@@ -10,10 +10,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
+import npz_parts
 import rgca_shaped as S
 from oracle import cref
 
-G = np.load(os.path.join(ROOT, "tests", "golden", "rgca_model_golden.npz"))
+G = npz_parts.load(os.path.join(ROOT, "tests", "golden", "rgca_model_golden.npz"))
 t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
 h = lambda x: hashlib.sha1(np.ascontiguousarray(x.numpy()).tobytes()).hexdigest()[:12]
 batch = S.batch_inputs(2, 0)

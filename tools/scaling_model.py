@@ -29,7 +29,7 @@ GRAD_FLOATS = 60_000_000 + 250_000 * 3
 
 
 def measure(views, steps, warmup):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--views", str(views), "--no-secondary", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--views", str(views), "--no-secondary", "--no-cpu-baseline",
            "--steps", str(steps), "--warmup", str(warmup)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -7,7 +7,7 @@
 TAG=${1:-wb}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 python -c "from goliath_amd import build; print(build.source_digest())" > $OUT/csrc_sha16.txt
-M="python bench.py --micro 1 --no-graph --no-cpu-baseline --no-secondary --steps 3 --warmup 1 $@"
+M="python bench.py --full --micro 1 --no-graph --no-cpu-baseline --no-secondary --steps 3 --warmup 1 $@"
 i=0
 for set in \
   "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VALU" \
