@@ -13,20 +13,17 @@ Host/device contract: Gaussian attributes are fp32 [B,N,.] tensors resident in H
 view matrices are read by the kernels from device memory.
 """
 import ctypes
+import math
 import os
 
 import torch
 
 from . import _lib, views as _views
-from ._lib import c_float, c_i64, c_int, fptr, iptr, ptr, stream_ptr
+from ._lib import c_float, c_i64, c_int, fptr, ptr, stream_ptr
 
 BLOCK = 16  # tile width; the reference's only value (render_gsplat.py:28)
 GRAD_RECORD = 16  # include/goliath_hip.h: GOL_GRAD_RECORD
 SPLAT_RECORD = 16  # include/goliath_hip.h: GOL_SPLAT_RECORD (the rasterizer's packed per-Gaussian record, 64 bytes)
-# pixels per lane of the raster kernels where this module calls them stage by stage (include/goliath_hip.h: 0 = chosen by
-# the number of views in the launch -- what gol_render_fwd / bwd always use; tests set 1 or 2 to pin a footprint)
-RASTER_PPL = 0
-
 
 def _tiles(img_h, img_w, block=BLOCK):
     return ((img_w + block - 1) // block) * ((img_h + block - 1) // block)
@@ -196,37 +193,86 @@ class _Workspace:
         self.reach = torch.empty(B, max(N, 1), dtype=torch.int64, device=device)  # pass-1 -> pass-3 tile masks
 
 
+# One marshaller per C-ABI entry called stage by stage: the header's positional order lives here only.  Keywords are the
+# header's names (block = BLOCK, stream = the current one); a pointer is a GPU tensor (checked), a device address or None.
+_F32, _I32, _I64, _U8 = torch.float32, torch.int32, torch.int64, torch.uint8
+
+
+def _p(x, dtype=_F32, name="tensor"):
+    return ctypes.c_void_p(x) if x is None or isinstance(x, int) else ptr(x, dtype, name)
+
+
+def _abi_bin_sort(*, B, N, xys, depths, radii, conics=None, opacities=None, img_h, img_w, capacity, tile_count, tile_bins,
+                  isect_keys, sorted_ids, n_isect, reach_scratch=None):
+    _lib.call("gol_bin_sort", c_int(B), c_int(N), _p(xys), _p(depths), _p(radii, _I32), _p(conics), _p(opacities),
+              c_int(img_h), c_int(img_w), c_int(BLOCK), c_i64(capacity), _p(tile_count, _I32), _p(tile_bins, _I32),
+              _p(isect_keys, _I64), _p(sorted_ids, _I32), _p(n_isect, _I32), _p(reach_scratch, _I64), stream_ptr())
+
+
+def _abi_project_fwd(*, B, N, means3d, scales, glob_scale, quats, viewmats, intrins, img_h, img_w, clip_thresh, cov3d=None,
+                     xys, depths, radii, conics, compensation, num_tiles_hit=None, opacities=None, opac_eff=None,
+                     colors=None, records=None):
+    _lib.call("gol_project_fwd", c_int(B), c_int(N), _p(means3d, name="means3d"), _p(scales, name="scales"),
+              c_float(glob_scale), _p(quats, name="quats"), _p(viewmats, name="viewmat"), _p(intrins, name="intrins"),
+              c_int(img_h), c_int(img_w), c_int(BLOCK), c_float(clip_thresh), _p(cov3d), _p(xys), _p(depths),
+              _p(radii, _I32), _p(conics), _p(compensation), _p(num_tiles_hit, _I32), _p(opacities, name="opacity"),
+              _p(opac_eff), _p(colors, name="colors"), _p(records), stream_ptr())
+
+
+def _abi_project_bwd(*, B, N, means3d, scales, glob_scale, quats, viewmats, intrins, cov3d=None, radii, conics, compensation,
+                     v_xy=None, v_depth=None, v_conic=None, v_compensation=None, opacities=None, v_opac_eff=None,
+                     grad_stride=0, v_mean3d, v_scale, v_quat, v_opacity=None):
+    _lib.call("gol_project_bwd", c_int(B), c_int(N), _p(means3d), _p(scales), c_float(glob_scale), _p(quats),
+              _p(viewmats), _p(intrins), _p(cov3d), _p(radii, _I32), _p(conics), _p(compensation), _p(v_xy), _p(v_depth),
+              _p(v_conic), _p(v_compensation), _p(opacities), _p(v_opac_eff), c_int(grad_stride), _p(v_mean3d),
+              _p(v_scale), _p(v_quat), _p(v_opacity), stream_ptr())
+
+
+def _abi_rasterize_fwd(*, B, N, img_h, img_w, planar, tile_bins, sorted_ids, capacity, records, with_extra, background,
+                       out_img, out_extra=None, final_Ts, final_idx, out_alpha=None, out_extra_norm=None, norm_lo=0.0,
+                       l1_target=None, l1_mask=None, l1_mask_c=0, l1_sign=None, l1_partial=None, l1_out=None,
+                       l1_scale=1.0, pixels_per_lane=0):
+    _lib.call("gol_rasterize_fwd", c_int(B), c_int(N), c_int(img_h), c_int(img_w), c_int(BLOCK), c_int(planar),
+              _p(tile_bins, _I32), _p(sorted_ids, _I32), c_i64(capacity), _p(records), c_int(with_extra),
+              _p(background), _p(out_img), _p(out_extra), _p(final_Ts), _p(final_idx, _I32), _p(out_alpha),
+              _p(out_extra_norm), c_float(norm_lo), _p(l1_target), _p(l1_mask), c_int(l1_mask_c), _p(l1_sign, _U8),
+              _p(l1_partial), _p(l1_out), c_float(l1_scale), c_int(pixels_per_lane), stream_ptr())
+
+
+def _abi_rasterize_bwd(*, B, N, img_h, img_w, planar, tile_bins, sorted_ids, capacity, records, with_extra, background,
+                       final_Ts, final_idx, v_out_img=None, v_out_extra=None, v_out_alpha=None, v_xy, v_conic, v_colors,
+                       v_extra=None, v_opacity, grad_stride=0, v_sign=None, v_sign_mask=None, v_sign_mask_c=0,
+                       v_img_scale=None, v_img_scale_mul=1.0, pixels_per_lane=0):
+    _lib.call("gol_rasterize_bwd", c_int(B), c_int(N), c_int(img_h), c_int(img_w), c_int(BLOCK), c_int(planar),
+              _p(tile_bins, _I32), _p(sorted_ids, _I32), c_i64(capacity), _p(records), c_int(with_extra), _p(background),
+              _p(final_Ts), _p(final_idx, _I32), _p(v_out_img), _p(v_out_extra), _p(v_out_alpha), _p(v_xy), _p(v_conic),
+              _p(v_colors), _p(v_extra), _p(v_opacity), c_int(grad_stride), _p(v_sign, _U8), _p(v_sign_mask),
+              c_int(v_sign_mask_c), _p(v_img_scale), c_float(v_img_scale_mul), c_int(pixels_per_lane), stream_ptr())
+
+
 def _bin_sort(B, N, xys, depths, radii, img_h, img_w, ws, conics=None, opacities=None):
     """conics + opacities given -> (Gaussian, tile) pairs that cannot reach alpha >= 1/255 are pruned
     (output-preserving); omitted -> gsplat's exact 3-sigma tile lists."""
-    _lib.call("gol_bin_sort", c_int(B), c_int(N), fptr(xys), fptr(depths), iptr(radii), fptr(conics),
-              fptr(opacities), c_int(img_h), c_int(img_w), c_int(BLOCK), c_i64(ws.capacity),
-              iptr(ws.tile_count), iptr(ws.tile_bins), ptr(ws.keys, torch.int64), iptr(ws.sorted_ids),
-              iptr(ws.n_isect), ptr(ws.reach, torch.int64), stream_ptr())
+    _abi_bin_sort(B=B, N=N, xys=xys, depths=depths, radii=radii, conics=conics, opacities=opacities, img_h=img_h,
+                  img_w=img_w, capacity=ws.capacity, tile_count=ws.tile_count, tile_bins=ws.tile_bins, isect_keys=ws.keys,
+                  sorted_ids=ws.sorted_ids, n_isect=ws.n_isect, reach_scratch=ws.reach)
 
 
 def _project_fwd(B, N, means, scales, glob_scale, quats, viewmats, intrins, img_h, img_w, clip,
                  opacities=None, colors=None):
     """colors (with opacities) given: also returns the rasterizer's packed records[B,N,16] (depth as the 4th channel)."""
-    dev = means.device
-    f = dict(dtype=torch.float32, device=dev)
+    f = dict(dtype=torch.float32, device=means.device)
     records = torch.empty(B, N, SPLAT_RECORD, **f) if colors is not None else None
-    cov3d = torch.empty(B, N, 6, **f)
-    xys = torch.empty(B, N, 2, **f)
-    depths = torch.empty(B, N, **f)
-    radii = torch.empty(B, N, dtype=torch.int32, device=dev)
-    conics = torch.empty(B, N, 3, **f)
-    comp = torch.empty(B, N, **f)
-    nth = torch.empty(B, N, dtype=torch.int32, device=dev)
+    cov3d, xys, conics = (torch.empty(B, N, k, **f) for k in (6, 2, 3))
+    depths, comp = torch.empty(B, N, **f), torch.empty(B, N, **f)
+    radii, nth = (torch.empty(B, N, dtype=torch.int32, device=means.device) for _ in range(2))
     opac_eff = torch.empty(B, N, **f) if opacities is not None else None
-    _lib.call("gol_project_fwd", c_int(B), c_int(N), fptr(means, "means3d"), fptr(scales, "scales"),
-              c_float(glob_scale), fptr(quats, "quats"), fptr(viewmats, "viewmat"), fptr(intrins, "intrins"),
-              c_int(img_h), c_int(img_w), c_int(BLOCK), c_float(clip), fptr(cov3d), fptr(xys), fptr(depths),
-              iptr(radii), fptr(conics), fptr(comp), iptr(nth), fptr(opacities, "opacity"), fptr(opac_eff),
-              fptr(colors, "colors"), fptr(records), stream_ptr())
-    if colors is not None:
-        return cov3d, xys, depths, radii, conics, comp, nth, opac_eff, records
-    return cov3d, xys, depths, radii, conics, comp, nth, opac_eff
+    _abi_project_fwd(B=B, N=N, means3d=means, scales=scales, glob_scale=glob_scale, quats=quats, viewmats=viewmats,
+                     intrins=intrins, img_h=img_h, img_w=img_w, clip_thresh=clip, cov3d=cov3d, xys=xys, depths=depths,
+                     radii=radii, conics=conics, compensation=comp, num_tiles_hit=nth, opacities=opacities,
+                     opac_eff=opac_eff, colors=colors, records=records)
+    out = (cov3d, xys, depths, radii, conics, comp, nth, opac_eff)
+    return out + (records,) if colors is not None else out
 
 
 def _pack_records(B, N, xys, conics, colors, extra, opacities):
@@ -277,11 +323,10 @@ class _ProjectGaussians(torch.autograd.Function):
         # converted gradients are bound to locals so they outlive the launch
         g_xy, g_depth, g_conic, g_comp = c(v_xys), c(v_depths), c(v_conics), c(v_compensation)
         with _lib.device_guard(means3d.device):
-            _lib.call("gol_project_bwd", c_int(1), c_int(N), fptr(means3d), fptr(scales), c_float(ctx.glob_scale),
-                      fptr(quats), fptr(vm), fptr(intr), fptr(cov3d), iptr(radii), fptr(conics), fptr(comp),
-                      fptr(g_xy), fptr(g_depth), fptr(g_conic), fptr(g_comp),
-                      fptr(None), fptr(None), c_int(0), fptr(v_mean), fptr(v_scale), fptr(v_quat), fptr(None),
-                      stream_ptr())
+            _abi_project_bwd(B=1, N=N, means3d=means3d, scales=scales, glob_scale=ctx.glob_scale, quats=quats, viewmats=vm,
+                             intrins=intr, cov3d=cov3d, radii=radii, conics=conics, compensation=comp, v_xy=g_xy,
+                             v_depth=g_depth, v_conic=g_conic, v_compensation=g_comp, v_mean3d=v_mean, v_scale=v_scale,
+                             v_quat=v_quat)
         return (v_mean, v_scale, None, v_quat) + (None,) * 9
 
 
@@ -324,12 +369,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             with _lib.device_guard(dev):
                 _bin_sort(1, N, xys, depths, radii, img_height, img_width, ws, conics, opacity)
                 records = _pack_records(1, N, xys, conics, colors, None, opacity)
-                _lib.call("gol_rasterize_fwd", c_int(1), c_int(N), c_int(img_height), c_int(img_width),
-                          c_int(BLOCK), c_int(0), iptr(ws.tile_bins), iptr(ws.sorted_ids), c_i64(ws.capacity),
-                          fptr(records), c_int(0), fptr(background),
-                          fptr(out_img), fptr(None), fptr(final_Ts), iptr(final_idx), fptr(None), fptr(None),
-                          c_float(0.0), fptr(None), fptr(None), c_int(0), fptr(None), fptr(None), fptr(None),
-                          c_float(1.0), c_int(RASTER_PPL), stream_ptr())
+                _abi_rasterize_fwd(B=1, N=N, img_h=img_height, img_w=img_width, planar=0, tile_bins=ws.tile_bins,
+                                   sorted_ids=ws.sorted_ids, capacity=ws.capacity, records=records, with_extra=0,
+                                   background=background, out_img=out_img, final_Ts=final_Ts, final_idx=final_idx)
             ctx.ws = ws
             ctx.save_for_backward(xys, conics, colors, opacity, background, final_Ts, final_idx, records)
             out_img, final_Ts = out_img[0], final_Ts[0]
@@ -353,12 +395,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             va = None if v_out_alpha is None else _f32c(v_out_alpha)
             vo = _f32c(v_out_img)
             with _lib.device_guard(xys.device):
-                _lib.call("gol_rasterize_bwd", c_int(1), c_int(N), c_int(H), c_int(W), c_int(BLOCK), c_int(0),
-                          iptr(ws.tile_bins), iptr(ws.sorted_ids), c_i64(ws.capacity), fptr(records), c_int(0),
-                          fptr(background), fptr(final_Ts),
-                          iptr(final_idx), fptr(vo), fptr(None), fptr(va), fptr(v_xy),
-                          fptr(v_conic), fptr(v_colors), fptr(None), fptr(v_opacity), c_int(0), fptr(None), fptr(None),
-                          c_int(0), fptr(None), c_float(1.0), c_int(RASTER_PPL), stream_ptr())
+                _abi_rasterize_bwd(B=1, N=N, img_h=H, img_w=W, planar=0, tile_bins=ws.tile_bins, sorted_ids=ws.sorted_ids,
+                                   capacity=ws.capacity, records=records, with_extra=0, background=background,
+                                   final_Ts=final_Ts, final_idx=final_idx, v_out_img=vo, v_out_alpha=va, v_xy=v_xy,
+                                   v_conic=v_conic, v_colors=v_colors, v_opacity=v_opacity)
         # ctx.ws stays: a second backward through this node (retain_graph=True, per-loss backward calls) needs the tile
         # lists again; autograd frees them with the graph
         return (v_xy, None, None, v_conic, None, v_colors, v_opacity[:, None]) + (None,) * 5
@@ -420,93 +460,68 @@ def _layout(B, N, img_h, img_w, capacity, with_l1, projected=False):
 
 def _ws_view(ws, off, dtype, shape):
     """Typed view of a workspace sub-buffer (no copy)."""
-    n = 1
-    for d in shape:
-        n *= d
-    return ws[off:off + n * torch.empty(0, dtype=dtype).element_size()].view(dtype).view(shape)
+    return ws[off:off + math.prod(shape) * dtype.itemsize].view(dtype).view(shape)
 
 
-def _render_fwd_stages(B, N, img_h, img_w, glob_scale, clip, means, scales, quats, opacity, colors, viewmats, intrins,
-                       background, with_depth, norm_lo, cap, ws, L, out_img, out_depth, alpha, depth_norm, l1_target,
-                       l1_mask, l1_mask_c, l1_partial, l1_out, l1_scale):
-    """gol_render_fwd, stage by stage (what csrc/render.hip composes), for per-stage event timing."""
-    p = lambda off: ctypes.c_void_p(ws.data_ptr() + off) if off >= 0 else ctypes.c_void_p(0)
-    _lib.call("gol_project_fwd", c_int(B), c_int(N), fptr(means), fptr(scales), c_float(glob_scale), fptr(quats),
-              fptr(viewmats), fptr(intrins), c_int(img_h), c_int(img_w), c_int(BLOCK), c_float(clip), p(L.cov3d),
-              p(L.xys), p(L.depths), p(L.radii), p(L.conics), p(L.comp), p(L.nth), fptr(opacity), p(L.opac_eff),
-              fptr(colors), p(L.records), stream_ptr())
-    _lib.call("gol_bin_sort", c_int(B), c_int(N), p(L.xys), p(L.depths), p(L.radii), p(L.conics), p(L.opac_eff),
-              c_int(img_h), c_int(img_w), c_int(BLOCK), c_i64(cap), p(L.tile_count), p(L.tile_bins), p(L.keys),
-              p(L.sorted_ids), p(L.n_isect), ctypes.c_void_p(0), stream_ptr())
-    _lib.call("gol_rasterize_fwd", c_int(B), c_int(N), c_int(img_h), c_int(img_w), c_int(BLOCK), c_int(1),
-              p(L.tile_bins), p(L.sorted_ids), c_i64(cap), p(L.records), c_int(1 if with_depth else 0), fptr(background),
-              fptr(out_img), fptr(out_depth), p(L.final_T), p(L.final_idx), fptr(alpha), fptr(depth_norm),
-              c_float(norm_lo), fptr(l1_target), fptr(l1_mask), c_int(l1_mask_c),
-              p(L.l1_sign) if l1_target is not None else ctypes.c_void_p(0), fptr(l1_partial), fptr(l1_out),
-              c_float(l1_scale), c_int(RASTER_PPL), stream_ptr())
+def _render_fwd_staged(B, N, src, attrs, background, with_depth, norm_lo, cap, ws, L, out_img, out_depth, alpha, depth_norm,
+                       l1_target, l1_mask, l1_mask_c, l1_partial, l1_out, l1_scale):
+    """gol_render_fwd[_projected] stage by stage (what csrc/render.hip composes), for _lib.TIMING.  src: the views'
+    gol_shade_proj; attrs = (means, scales, quats, opacity, colors): unfused, project them into `src` first."""
+    a = ws.data_ptr()
+    if attrs is not None:
+        means, scales, quats, opacity, colors = attrs
+        _abi_project_fwd(B=B, N=N, means3d=means, scales=scales, glob_scale=src.glob_scale, quats=quats,
+                         viewmats=src.viewmats, intrins=src.intrins, img_h=src.img_h, img_w=src.img_w,
+                         clip_thresh=src.clip_thresh, xys=src.xys, depths=src.depths, radii=src.radii, conics=src.conics,
+                         compensation=src.comp, opacities=opacity, opac_eff=src.opac_eff, colors=colors,
+                         records=src.records)
+    _abi_bin_sort(B=B, N=N, xys=src.xys, depths=src.depths, radii=src.radii, conics=src.conics, opacities=src.opac_eff,
+                  img_h=src.img_h, img_w=src.img_w, capacity=cap, tile_count=a + L.tile_count, tile_bins=a + L.tile_bins,
+                  isect_keys=a + L.keys, sorted_ids=a + L.sorted_ids, n_isect=a + L.n_isect)
+    _abi_rasterize_fwd(B=B, N=N, img_h=src.img_h, img_w=src.img_w, planar=1, tile_bins=a + L.tile_bins,
+                       sorted_ids=a + L.sorted_ids, capacity=cap, records=src.records, with_extra=int(with_depth),
+                       background=background, out_img=out_img, out_extra=out_depth, final_Ts=a + L.final_T,
+                       final_idx=a + L.final_idx, out_alpha=alpha, out_extra_norm=depth_norm, norm_lo=norm_lo,
+                       l1_target=l1_target, l1_mask=l1_mask, l1_mask_c=l1_mask_c,
+                       l1_sign=a + L.l1_sign if l1_target is not None else None, l1_partial=l1_partial, l1_out=l1_out,
+                       l1_scale=l1_scale)
 
 
-def _render_bwd_stages(B, N, img_h, img_w, glob_scale, means, scales, quats, opacity, viewmats, intrins, background, cap,
-                       ws, L, v_img, v_depth, v_alpha, use_l1, l1_mask, v_scale, v_scale_mul, rec, v_mean, v_scale_g, v_quat,
-                       v_opacity):
-    """gol_render_bwd, stage by stage, for per-stage event timing."""
-    p = lambda off: ctypes.c_void_p(ws.data_ptr() + off) if off >= 0 else ctypes.c_void_p(0)
-    field = lambda k: ctypes.c_void_p(rec.data_ptr() + 4 * k)
-    null = ctypes.c_void_p(0)
+def _render_bwd_staged(B, N, src, attrs, grads, background, cap, ws, L, v_img, v_depth, v_alpha, use_l1, l1_mask, v_scale,
+                       v_scale_mul, rec):
+    """gol_render_bwd[_projected] stage by stage: the raster backward into the zeroed records rec[B,N,GRAD_RECORD] (rgb |
+    opacity | xy | conic | depth | pad); unfused (attrs = (means, scales, quats, opacity)): the projection backward."""
+    a = ws.data_ptr()
+    field = lambda k: rec.data_ptr() + 4 * k
     use_depth = v_depth is not None
     rec.zero_()
-    _lib.call("gol_rasterize_bwd", c_int(B), c_int(N), c_int(img_h), c_int(img_w), c_int(BLOCK), c_int(1),
-              p(L.tile_bins), p(L.sorted_ids), c_i64(cap), p(L.records), c_int(1 if use_depth else 0), fptr(background),
-              p(L.final_T), p(L.final_idx), fptr(v_img), fptr(v_depth), fptr(v_alpha), field(4), field(6), field(0),
-              field(9) if use_depth else null, field(3), c_int(GRAD_RECORD), p(L.l1_sign) if use_l1 else null,
-              fptr(l1_mask) if use_l1 else null, c_int(0 if (l1_mask is None or not use_l1) else l1_mask.shape[1]),
-              fptr(v_scale), c_float(v_scale_mul), c_int(0), stream_ptr())
-    _lib.call("gol_project_bwd", c_int(B), c_int(N), fptr(means), fptr(scales), c_float(glob_scale), fptr(quats),
-              fptr(viewmats), fptr(intrins), p(L.cov3d), p(L.radii), p(L.conics), p(L.comp), field(4),
-              field(9) if use_depth else null, field(6), null, fptr(opacity), field(3), c_int(GRAD_RECORD), fptr(v_mean),
-              fptr(v_scale_g), fptr(v_quat), fptr(v_opacity), stream_ptr())
-
-
-def _render_fwd_stages_projected(B, N, img_h, img_w, pj, background, with_depth, norm_lo, cap, ws, L, out_img, out_depth,
-                                 alpha, depth_norm, l1_target, l1_mask, l1_mask_c, l1_partial, l1_out, l1_scale):
-    """gol_render_fwd_projected, stage by stage (per-stage event timing)."""
-    p = lambda off: ctypes.c_void_p(ws.data_ptr() + off) if off >= 0 else ctypes.c_void_p(0)
-    v = ctypes.c_void_p
-    _lib.call("gol_bin_sort", c_int(B), c_int(N), v(pj.xys), v(pj.depths), v(pj.radii), v(pj.conics), v(pj.opac_eff),
-              c_int(img_h), c_int(img_w), c_int(BLOCK), c_i64(cap), p(L.tile_count), p(L.tile_bins), p(L.keys),
-              p(L.sorted_ids), p(L.n_isect), ctypes.c_void_p(0), stream_ptr())
-    _lib.call("gol_rasterize_fwd", c_int(B), c_int(N), c_int(img_h), c_int(img_w), c_int(BLOCK), c_int(1),
-              p(L.tile_bins), p(L.sorted_ids), c_i64(cap), v(pj.records), c_int(1 if with_depth else 0), fptr(background),
-              fptr(out_img), fptr(out_depth), p(L.final_T), p(L.final_idx), fptr(alpha), fptr(depth_norm),
-              c_float(norm_lo), fptr(l1_target), fptr(l1_mask), c_int(l1_mask_c),
-              p(L.l1_sign) if l1_target is not None else ctypes.c_void_p(0), fptr(l1_partial), fptr(l1_out),
-              c_float(l1_scale), c_int(RASTER_PPL), stream_ptr())
-
-
-def _render_bwd_stages_projected(B, N, img_h, img_w, pj, background, cap, ws, L, v_img, v_depth, v_alpha, use_l1, l1_mask,
-                                 v_scale, v_scale_mul, rec):
-    """gol_render_bwd_projected, stage by stage."""
-    p = lambda off: ctypes.c_void_p(ws.data_ptr() + off) if off >= 0 else ctypes.c_void_p(0)
-    field = lambda k: ctypes.c_void_p(rec.data_ptr() + 4 * k)
-    null = ctypes.c_void_p(0)
-    use_depth = v_depth is not None
-    rec.zero_()
-    _lib.call("gol_rasterize_bwd", c_int(B), c_int(N), c_int(img_h), c_int(img_w), c_int(BLOCK), c_int(1),
-              p(L.tile_bins), p(L.sorted_ids), c_i64(cap), ctypes.c_void_p(pj.records), c_int(1 if use_depth else 0),
-              fptr(background), p(L.final_T), p(L.final_idx), fptr(v_img), fptr(v_depth), fptr(v_alpha), field(4), field(6),
-              field(0), field(9) if use_depth else null, field(3), c_int(GRAD_RECORD), p(L.l1_sign) if use_l1 else null,
-              fptr(l1_mask) if use_l1 else null, c_int(0 if (l1_mask is None or not use_l1) else l1_mask.shape[1]),
-              fptr(v_scale), c_float(v_scale_mul), c_int(0), stream_ptr())
+    _abi_rasterize_bwd(B=B, N=N, img_h=src.img_h, img_w=src.img_w, planar=1, tile_bins=a + L.tile_bins,
+                       sorted_ids=a + L.sorted_ids, capacity=cap, records=src.records, with_extra=int(use_depth),
+                       background=background, final_Ts=a + L.final_T, final_idx=a + L.final_idx, v_out_img=v_img,
+                       v_out_extra=v_depth, v_out_alpha=v_alpha, v_xy=field(4), v_conic=field(6), v_colors=field(0),
+                       v_extra=field(9) if use_depth else None, v_opacity=field(3), grad_stride=GRAD_RECORD,
+                       v_sign=a + L.l1_sign if use_l1 else None, v_sign_mask=l1_mask,
+                       v_sign_mask_c=0 if l1_mask is None else l1_mask.shape[1], v_img_scale=v_scale,
+                       v_img_scale_mul=v_scale_mul)
+    if attrs is not None:
+        means, scales, quats, opacity = attrs
+        v_mean, v_scale_g, v_quat, v_opacity = grads
+        _abi_project_bwd(B=B, N=N, means3d=means, scales=scales, glob_scale=src.glob_scale, quats=quats,
+                         viewmats=src.viewmats, intrins=src.intrins, radii=src.radii, conics=src.conics,
+                         compensation=src.comp, v_xy=field(4), v_depth=field(9) if use_depth else None, v_conic=field(6),
+                         opacities=opacity, v_opac_eff=field(3), grad_stride=GRAD_RECORD, v_mean3d=v_mean,
+                         v_scale=v_scale_g, v_quat=v_quat, v_opacity=v_opacity)
 
 
 class _RenderViews(torch.autograd.Function):
     """The fused path: ONE C-ABI call per direction (gol_render_fwd / gol_render_bwd, csrc/render.hip) out of one
-    workspace allocation; the host work of a direction is that call plus the allocation of its outputs."""
+    workspace allocation; the host work of a direction is that call plus the allocation of its outputs.  With
+    _lib.TIMING set (bench.py's instrumented pass) the same work runs as one ABI call per stage instead."""
 
     @staticmethod
     def forward(ctx, means, scales, quats, opacity, colors, viewmats, intrins, background, img_h, img_w,
                 glob_scale, clip_thresh, with_depth, capacity, depth_norm_lo, plan_key, l1_target, l1_mask,
-                raw_depth=True, records=None, pack=None, view_set=None):
+                raw_depth, records, pack, view_set, res):
         # records / pack / view_set given (a views.Projected): the Gaussians were projected by the shading kernel -- means ...
         # colors are None, the call starts at the tile count and its backward ends at the gradient records (= the gradient of
         # `records`, which the shading backward pushes through the projection's vjp)
@@ -514,6 +529,7 @@ class _RenderViews(torch.autograd.Function):
         B, N = (records if projected else means).shape[:2]
         dev = (records if projected else means).device
         pj = _views.proj_struct(view_set, records, pack) if projected else None
+        attrs = None if projected else (means, scales, quats, opacity, colors)
         T = _tiles(img_h, img_w)
         with_l1 = 1 if l1_target is not None else 0
         f = dict(dtype=torch.float32, device=dev)
@@ -533,34 +549,29 @@ class _RenderViews(torch.autograd.Function):
         def run(cap):
             L = _layout(B, N, img_h, img_w, cap, with_l1, projected)
             ws = torch.empty(max(L.total, 1), dtype=torch.uint8, device=dev)
-            if projected and _lib.TIMING is not None:
-                _render_fwd_stages_projected(B, N, img_h, img_w, pj, background, with_depth, depth_norm_lo, cap, ws, L,
-                                             out_img, out_depth, alpha, depth_norm, l1_target, l1_mask, l1_mask_c,
-                                             l1_partial, l1_out, l1_inv_n)
-            elif projected:
-                _lib.call("gol_render_fwd_projected", c_int(B), c_int(N), ctypes.byref(pj), fptr(background),
-                          c_int(1 if with_depth else 0), c_float(depth_norm_lo), c_i64(cap),
+            # the cameras and screen-space buffers the call bins and rasterizes; unfused: projected into the workspace
+            a = ws.data_ptr()
+            src = pj if projected else _views.ShadeProj(
+                fptr(viewmats).value, fptr(intrins).value, img_h, img_w, glob_scale, clip_thresh, a + L.xys, a + L.depths,
+                a + L.radii, a + L.conics, a + L.comp, a + L.opac_eff, a + L.records)
+            if _lib.TIMING is not None:
+                _render_fwd_staged(B, N, src, attrs, background, with_depth, depth_norm_lo, cap, ws, L, out_img, out_depth,
+                                   alpha, depth_norm, l1_target, l1_mask, l1_mask_c, l1_partial, l1_out, l1_inv_n)
+            else:
+                entry = (("gol_render_fwd_projected", c_int(B), c_int(N), ctypes.byref(pj)) if projected else
+                         ("gol_render_fwd", c_int(B), c_int(N), c_int(img_h), c_int(img_w), c_float(glob_scale),
+                          c_float(clip_thresh), fptr(means), fptr(scales), fptr(quats), fptr(opacity), fptr(colors),
+                          fptr(viewmats), fptr(intrins)))
+                _lib.call(*entry, fptr(background), c_int(1 if with_depth else 0), c_float(depth_norm_lo), c_i64(cap),
                           ctypes.c_void_p(ws.data_ptr()), ctypes.byref(L), fptr(out_img), fptr(out_depth), fptr(alpha),
                           fptr(depth_norm), fptr(l1_target), fptr(l1_mask), c_int(l1_mask_c), fptr(l1_partial),
                           fptr(l1_out), c_float(l1_inv_n), stream_ptr())
-            elif _lib.TIMING is not None:
-                # instrumented pass (bench.py): the same work as three ABI calls, so that events bracket each stage
-                _render_fwd_stages(B, N, img_h, img_w, glob_scale, clip_thresh, means, scales, quats, opacity, colors,
-                                   viewmats, intrins, background, with_depth, depth_norm_lo, cap, ws, L, out_img,
-                                   out_depth, alpha, depth_norm, l1_target, l1_mask, l1_mask_c, l1_partial, l1_out, l1_inv_n)
-            else:
-                _lib.call("gol_render_fwd", c_int(B), c_int(N), c_int(img_h), c_int(img_w), c_float(glob_scale),
-                          c_float(clip_thresh), fptr(means), fptr(scales), fptr(quats), fptr(opacity), fptr(colors),
-                          fptr(viewmats), fptr(intrins), fptr(background), c_int(1 if with_depth else 0),
-                          c_float(depth_norm_lo), c_i64(cap), ctypes.c_void_p(ws.data_ptr()), ctypes.byref(L),
-                          fptr(out_img), fptr(out_depth), fptr(alpha), fptr(depth_norm), fptr(l1_target), fptr(l1_mask),
-                          c_int(l1_mask_c), fptr(l1_partial), fptr(l1_out), c_float(l1_inv_n), stream_ptr())
             n_isect = _ws_view(ws, L.n_isect, torch.int32, (B,))
             pending = PLANNER.fetch(n_isect) if plan_key is not None and B > 0 else None
-            return ws, L, n_isect, pending
+            return ws, L, src, n_isect, pending
 
         with _lib.device_guard(dev):
-            ws, L, n_isect, pending = run(capacity)
+            ws, L, src, n_isect, pending = run(capacity)
             if pending is not None:
                 # the counts were final after the tile scan; the raster is still queued behind this wait
                 worst = PLANNER.finish(*pending)
@@ -570,16 +581,17 @@ class _RenderViews(torch.autograd.Function):
                     capacity = PLANNER.set(plan_key, worst)
                     PLANNER.last_worst[plan_key] = worst
                     PLANNER.reruns += 1
-                    ws, L, n_isect, pending = run(capacity)
+                    ws, L, src, n_isect, pending = run(capacity)
                     PLANNER.finish(*pending)
                 else:
                     PLANNER.observe(plan_key, worst, capacity)
                 PLANNER.passed(plan_key)
-        ctx.L, ctx.capacity = L, capacity
+        res.bind((B, N, img_h, img_w, T), ws, L, capacity, src, pack if projected else ws, records if projected else ws)
+        ctx.L, ctx.capacity, ctx.src = L, capacity, src
         ctx.cfg = (img_h, img_w, glob_scale, with_depth, depth_norm_lo, with_l1)
         ctx.l1_inv_n = l1_inv_n
         l1 = l1_out.reshape(()) if with_l1 else None  # == mean(|(rgb - target) * mask|)
-        ctx.view_set = view_set
+        ctx.view_set = view_set   # (keeps the cameras `src` points at alive)
         ctx.save_for_backward(means, scales, quats, opacity, viewmats, intrins, background, ws, l1_mask, records, pack)
         ctx.mark_non_differentiable(ws, n_isect)
         ctx.set_materialize_grads(False)
@@ -600,7 +612,7 @@ class _RenderViews(torch.autograd.Function):
         if not with_l1:
             v_l1 = None
         if v_img is None and v_alpha is None and v_depth is None and v_l1 is None:
-            return (None,) * 22
+            return (None,) * 23
         # fused L1: d loss / d rgb = (sign code - 1) * mask * (v_l1 / n).  The raster backward decodes the sign bytes itself
         # and adds the term to v_img (if the image has another consumer); the scalar goes in as a device value: no sync,
         # no pass over the image
@@ -619,58 +631,50 @@ class _RenderViews(torch.autograd.Function):
         # float atomics hit one cache line and are issued by 16 adjacent lanes
         rec = torch.empty(B, N, GRAD_RECORD, device=dev)
         use_mask = l1_mask if v_l1 is not None else None
-        if projected:
-            pj = _views.proj_struct(ctx.view_set, records, pack)
-            with _lib.device_guard(dev):
-                if _lib.TIMING is not None:
-                    _render_bwd_stages_projected(B, N, img_h, img_w, pj, background, ctx.capacity, ws, L, v_img_c, v_depth_c,
-                                                 v_alpha_c, v_l1 is not None, use_mask, v_scale, ctx.l1_inv_n, rec)
-                else:
-                    _lib.call("gol_render_bwd_projected", c_int(B), c_int(N), ctypes.byref(pj), fptr(background),
-                              c_i64(ctx.capacity), ctypes.c_void_p(ws.data_ptr()), ctypes.byref(L), fptr(v_img_c),
-                              fptr(v_depth_c), fptr(v_alpha_c), c_int(1 if v_l1 is not None else 0), fptr(use_mask),
-                              c_int(0 if use_mask is None else use_mask.shape[1]), fptr(v_scale), c_float(ctx.l1_inv_n),
-                              fptr(rec), stream_ptr())
-            return (None,) * 19 + (rec, None, None)
-        v_mean = torch.empty_like(means)
-        v_scale_g = torch.empty_like(scales)
-        v_quat = torch.empty_like(quats)
-        v_opacity = torch.empty_like(opacity)
-        if _lib.TIMING is not None:
-            with _lib.device_guard(dev):
-                _render_bwd_stages(B, N, img_h, img_w, glob_scale, means, scales, quats, opacity, viewmats, intrins,
-                                   background, ctx.capacity, ws, L, v_img_c, v_depth_c, v_alpha_c, v_l1 is not None,
-                                   use_mask, v_scale, ctx.l1_inv_n, rec, v_mean, v_scale_g, v_quat, v_opacity)
-            return (v_mean, v_scale_g, v_quat, v_opacity, rec[..., :3]) + (None,) * 17
-        v_color = torch.empty(B, N, 3, device=dev)  # dense copy of the records' colour gradient (written by the projection backward)
+        attrs = None if projected else (means, scales, quats, opacity)
+        grads = None if projected else tuple(torch.empty_like(t) for t in attrs)   # v_mean, v_scale, v_quat, v_opacity
         with _lib.device_guard(dev):
-            _lib.call("gol_render_bwd", c_int(B), c_int(N), c_int(img_h), c_int(img_w), c_float(glob_scale), fptr(means),
-                      fptr(scales), fptr(quats), fptr(opacity), fptr(viewmats), fptr(intrins), fptr(background),
-                      c_i64(ctx.capacity), ctypes.c_void_p(ws.data_ptr()), ctypes.byref(L), fptr(v_img_c),
-                      fptr(v_depth_c), fptr(v_alpha_c), c_int(1 if v_l1 is not None else 0), fptr(use_mask),
-                      c_int(0 if use_mask is None else use_mask.shape[1]), fptr(v_scale), c_float(ctx.l1_inv_n), fptr(rec),
-                      fptr(v_mean),
-                      fptr(v_scale_g), fptr(v_quat), fptr(v_opacity), fptr(v_color), stream_ptr())
+            if _lib.TIMING is not None:
+                _render_bwd_staged(B, N, ctx.src, attrs, grads, background, ctx.capacity, ws, L, v_img_c, v_depth_c,
+                                   v_alpha_c, v_l1 is not None, use_mask, v_scale, ctx.l1_inv_n, rec)
+                v_color = None if projected else rec[..., :3]   # (the single call writes a dense copy instead)
+            else:
+                shared = (fptr(background), c_i64(ctx.capacity), ctypes.c_void_p(ws.data_ptr()), ctypes.byref(L),
+                          fptr(v_img_c), fptr(v_depth_c), fptr(v_alpha_c), c_int(1 if v_l1 is not None else 0),
+                          fptr(use_mask), c_int(0 if use_mask is None else use_mask.shape[1]), fptr(v_scale),
+                          c_float(ctx.l1_inv_n), fptr(rec))
+                if projected:
+                    _lib.call("gol_render_bwd_projected", c_int(B), c_int(N), ctypes.byref(ctx.src), *shared, stream_ptr())
+                else:
+                    # dense copy of the records' colour gradient (written by the projection backward)
+                    v_color = torch.empty(B, N, 3, device=dev)
+                    _lib.call("gol_render_bwd", c_int(B), c_int(N), c_int(img_h), c_int(img_w), c_float(glob_scale),
+                              fptr(means), fptr(scales), fptr(quats), fptr(opacity), fptr(viewmats), fptr(intrins), *shared,
+                              *(fptr(g) for g in grads), fptr(v_color), stream_ptr())
         # (the workspace stays alive with the node: retain_graph / a second backward re-reads the tile lists)
-        return (v_mean, v_scale_g, v_quat, v_opacity, v_color) + (None,) * 17
+        if projected:
+            return (None,) * 19 + (rec, None, None, None)
+        return grads + (v_color,) + (None,) * 18
 
 
 _BLACK = {}
 
 
 class _LazyRender(dict):
-    """Result of render_views: the images are plain entries; the diagnostics (typed views into the call's workspace:
+    """Result of render_views: the images are plain entries; the diagnostics (typed views into the call's buffers:
     radii, final_T, final_idx, sorted_ids, tile_bins) are created on first access."""
 
-    def __init__(self, ws, layout, dims, capacity, projected=None):
-        super().__init__()
-        self._ws, self._L, self._dims, self._cap, self._proj = ws, layout, dims, capacity, projected
+    def bind(self, dims, ws, L, cap, src, arrays, records):
+        """What the forward rendered with: workspace, layout, capacity, and the gol_shade_proj `src` whose per-Gaussian
+        arrays and records live in the tensors `arrays` and `records` (the workspace, or a Projected's pack and records)."""
+        self._dims, self._ws, self._L, self._cap, self._src, self._arrays, self._records = dims, ws, L, cap, src, arrays, records
 
     def __missing__(self, key):
         B, N, H, W, T = self._dims
         ws, L = self._ws, self._L
         if key == "radii":
-            v = _ws_view(ws, L.radii, torch.int32, (B, N)) if self._proj is None else self._proj.field("radii")
+            buf = self._arrays.view(-1).view(torch.uint8)   # the workspace, or a views.Projected's pack
+            v = _ws_view(buf, (self._src.radii or 0) - buf.data_ptr(), torch.int32, (B, N))
         elif key == "final_T":
             v = _ws_view(ws, L.final_T, torch.float32, (B, 1, H, W))
         elif key == "final_idx":
@@ -690,12 +694,12 @@ def raster_pair_counts(res):
     pixel's final_idx) and took (alpha >= 1/255) -- gol_raster_count_pairs on the call's workspace."""
     B, N, H, W, T = res._dims
     ws, L = res._ws, res._L
+    a = ws.data_ptr()
     counts = torch.empty(B, 2, dtype=torch.int64, device=ws.device)
-    p = lambda off: ctypes.c_void_p(ws.data_ptr() + off)
-    rec = p(L.records) if res._proj is None else fptr(res._proj.records)
     with _lib.device_guard(ws.device):
-        _lib.call("gol_raster_count_pairs", c_int(B), c_int(N), c_int(H), c_int(W), p(L.tile_bins), p(L.sorted_ids),
-                  c_i64(res._cap), rec, p(L.final_idx), ptr(counts, torch.int64), stream_ptr())
+        _lib.call("gol_raster_count_pairs", c_int(B), c_int(N), c_int(H), c_int(W), _p(a + L.tile_bins),
+                  _p(a + L.sorted_ids), c_i64(res._cap), _p(res._src.records), _p(a + L.final_idx), _p(counts, _I64),
+                  stream_ptr())
     return counts
 
 
@@ -768,23 +772,17 @@ def render_views(means, scales, quats, opacity, colors, viewmats, intrins, img_h
                 raise ValueError("l1_mask must be [B,1,H,W] or [B,3,H,W]")
     else:
         l1_mask = None
-    out = _RenderViews.apply(means, scales, quats, opacity, colors, viewmats, intrins, background, img_h,
-                             img_w, float(glob_scale), float(clip_thresh), bool(with_depth), int(capacity),
-                             float(depth_norm_lo), plan_key, l1_target, l1_mask, bool(raw_depth),
-                             None if projected is None else projected.records,
-                             None if projected is None else projected.pack,
-                             None if projected is None else projected.views)
-    img, alpha, depth, depth_norm, l1, ws, n_isect = out
-    with_l1 = 1 if l1_target is not None else 0
-    is_proj = projected is not None
-    if plan_key is not None and max(_layout(B, N, img_h, img_w, capacity, with_l1, is_proj).total, 1) != ws.numel():
-        capacity = PLANNER.get(key)   # the checked call re-ran at a grown capacity: that is the workspace's layout
+    res = _LazyRender()
+    img, alpha, depth, depth_norm, l1, _, n_isect = _RenderViews.apply(
+        means, scales, quats, opacity, colors, viewmats, intrins, background, img_h, img_w, float(glob_scale),
+        float(clip_thresh), bool(with_depth), int(capacity), float(depth_norm_lo), plan_key, l1_target, l1_mask,
+        bool(raw_depth), None if projected is None else projected.records, None if projected is None else projected.pack,
+        None if projected is None else projected.views, res)
+    # res._cap: the capacity the forward rendered with (grown if the checked call had to re-run)
     if PLANNER.frozen:
-        PLANNER.frozen_log.append((n_isect, capacity))
+        PLANNER.frozen_log.append((n_isect, res._cap))
     elif deferred and B > 0:
-        PLANNER.note(key, n_isect, capacity)
-    res = _LazyRender(ws, _layout(B, N, img_h, img_w, capacity, with_l1, is_proj), (B, N, img_h, img_w, T), capacity,
-                      projected)
+        PLANNER.note(key, n_isect, res._cap)
     res["render"], res["alpha"], res["n_isect"] = img, alpha[:, None], n_isect
     # per-pixel index of the last contributor in its view's depth-sorted list, and that list: res["final_idx"],
     # res["sorted_ids"], res["tile_bins"], res["final_T"], res["radii"] (views into the call's workspace, made on access)

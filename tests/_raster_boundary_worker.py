@@ -5,7 +5,6 @@ product build) and prints one JSON line.  Production configuration of the kernel
 pass, L1 fused into the epilogue, 64-byte gradient records.
 
 usage: python _raster_boundary_worker.py VIEWS"""
-import ctypes
 import json
 import os
 import sys
@@ -28,7 +27,6 @@ PPL = int(os.environ.get("RASTER_BOUNDARY_PPL", "2"))   # wave footprint of the 
 def main(n_views):
     import bench
     from goliath_amd import _lib, splat
-    from goliath_amd._lib import c_float, c_i64, c_int, fptr, iptr, ptr, stream_ptr
     from oracle import cref, shade_ref
 
     cfg = dict(bench.CFG, views_per_gpu=1)
@@ -82,19 +80,16 @@ def main(n_views):
             sign = torch.empty(1, H, W, dtype=torch.uint8, device=dev)
             part = torch.empty(1, T, device=dev)
             records = splat._pack_records(1, N, d_xy, d_con, d_col, d_dep, d_op)
-            _lib.call("gol_rasterize_fwd", c_int(1), c_int(N), c_int(H), c_int(W), c_int(16), c_int(1),
-                      iptr(ws.tile_bins), iptr(ws.sorted_ids), c_i64(ws.capacity), fptr(records), c_int(1),
-                      fptr(bgd), fptr(out_img), fptr(None), fptr(fT), iptr(fidx), fptr(alpha),
-                      fptr(dnorm), c_float(0.05), fptr(d_tgt), fptr(None), c_int(0), ptr(sign, torch.uint8), fptr(part),
-                      fptr(None), c_float(1.0), c_int(PPL), stream_ptr())
+            lists = dict(B=1, N=N, img_h=H, img_w=W, planar=1, tile_bins=ws.tile_bins, sorted_ids=ws.sorted_ids,
+                         capacity=ws.capacity, records=records, background=bgd, final_Ts=fT, final_idx=fidx,
+                         pixels_per_lane=PPL)
+            splat._abi_rasterize_fwd(**lists, with_extra=1, out_img=out_img, out_alpha=alpha, out_extra_norm=dnorm,
+                                     norm_lo=0.05, l1_target=d_tgt, l1_sign=sign, l1_partial=part)
             rec = torch.zeros(1, N, 16, device=dev)
-            field = lambda k: ctypes.c_void_p(rec.data_ptr() + 4 * k)
+            field = lambda k: rec.data_ptr() + 4 * k
             vsc = torch.full((1,), scale, device=dev)
-            _lib.call("gol_rasterize_bwd", c_int(1), c_int(N), c_int(H), c_int(W), c_int(16), c_int(1),
-                      iptr(ws.tile_bins), iptr(ws.sorted_ids), c_i64(ws.capacity), fptr(records), c_int(0),
-                      fptr(bgd), fptr(fT), iptr(fidx), fptr(None), fptr(None), fptr(None),
-                      field(4), field(6), field(0), fptr(None), field(3), c_int(16), ptr(sign, torch.uint8), fptr(None),
-                      c_int(0), fptr(vsc), c_float(1.0), c_int(PPL), stream_ptr())
+            splat._abi_rasterize_bwd(**lists, with_extra=0, v_xy=field(4), v_conic=field(6), v_colors=field(0),
+                                     v_opacity=field(3), grad_stride=16, v_sign=sign, v_img_scale=vsc)
             torch.cuda.synchronize()
             n_isect_hip += int(ws.n_isect[0])
             Th = fT[0].cpu()

@@ -323,3 +323,79 @@ def test_render_batch_matches_per_view_loop():
         assert rel_l2(rgb[b], o["render"]) < 1e-6
         assert rel_l2(alpha[b], a) < 1e-6
         assert rel_l2(depth[b], o["depth"] / a.clamp(0.05, 1.0)) < 1e-6
+
+
+@pytest.mark.parametrize("with_l1", [False, True])
+@pytest.mark.parametrize("fused", [False, True])
+def test_instrumented_pass_equals_the_single_call(fused, with_l1):
+    """bench.py's per-call numbers come from the instrumented pass (_lib.TIMING set: one ABI call per stage).  It must
+    compute what the single-call path computes -- identical tile lists and images, leaf gradients up to the order of the
+    float atomics -- and make the calls bench.py keys on, in this order.  Unfused: render_views of the attributes; fused: the
+    shading kernel projects (shading_tail(..., views=...)) and the render starts at the tile count."""
+    import bench
+    from goliath_amd import _lib, render_gs, shade, splat
+
+    B, S, H, W = 2, 48, 160, 112
+    N, cap = S * S, 1 << 18
+    g = torch.Generator().manual_seed(21)
+    target, mask = torch.rand(B, 3, H, W, generator=g).cuda(), (torch.rand(B, 1, H, W, generator=g) > 0.3).float().cuda()
+    kw = dict(with_depth=True, capacity=cap, **(dict(l1_target=target, l1_mask=mask) if with_l1 else {}))
+    if fused:
+        cfg = dict(bench.CFG, gaussians=N, slab=S, height=H, width=W, views_per_gpu=B, focal=3000.0 * W / 1334.0, seed=5)
+        t = bench.make_inputs(cfg, torch.device("cuda"))
+        leaves = [t[k] for k in ("f_vn", "f_vc", "postex", "tn", "albedo")]
+        vs = render_gs.view_set(t["K"], t["Rt"], H, W)
+        lights = dict(light_intensity=(0.5 + torch.rand(B, 3, 1, generator=g)).cuda(),
+                      headrel_light_pos=(400.0 * torch.randn(B, 3, 3, generator=g)).cuda(),
+                      n_lights=torch.tensor([3, 2], dtype=torch.int32).cuda())
+
+        def render():
+            preds = shade.shading_tail(*leaves, t["light_sh"], t["campos"], views=vs, **lights)
+            return splat.render_views(None, None, None, None, None, None, None, H, W, raw_depth=False,
+                                      projected=preds["projected"], **kw)
+        calls = ["gol_bin_sort", "gol_rasterize_fwd", "gol_rasterize_bwd"]
+    else:
+        views = [head_scene(N, H, W, seed=30 + b, cam_angle=0.4 * b) for b in range(B)]
+        leaves = [torch.stack([v[k] for v in views]).cuda().requires_grad_(True)
+                  for k in ("means", "scales", "quats", "opacity", "colors")]
+        viewmats = torch.stack([v["viewmat"] for v in views]).cuda()
+        intrins = torch.tensor([[v["fx"], v["fy"], v["cx"], v["cy"]] for v in views]).cuda()
+
+        def render():
+            return splat.render_views(*leaves, viewmats, intrins, H, W, **kw)
+        calls = ["gol_project_fwd", "gol_bin_sort", "gol_rasterize_fwd", "gol_rasterize_bwd", "gol_project_bwd"]
+    w = [torch.randn(B, c, H, W, generator=g).cuda() for c in (3, 1, 1)]
+
+    def run(timing):
+        for x in leaves:
+            x.grad = None
+        _lib.TIMING = [] if timing else None
+        try:
+            out = render()
+            loss = (out["render"] * w[0]).sum() + (out["alpha"] * w[1]).sum() + (out["depth_norm"] * w[2]).sum()
+            (loss + out["l1_loss"] if with_l1 else loss).backward()
+            names = [n for n, _, _ in _lib.TIMING] if timing else None
+        finally:
+            _lib.TIMING = None
+        return out, [x.grad.clone() for x in leaves], names
+
+    plain, g0, _ = run(False)
+    inst, g1, names = run(True)
+    assert [n for n in names if not n.startswith("gol_shade_")] == calls
+    n_isect = plain["n_isect"]
+    assert torch.equal(inst["n_isect"], n_isect) and 0 < int(n_isect.min()) and int(n_isect.max()) <= cap
+    assert torch.equal(inst["tile_bins"], plain["tile_bins"])
+    for b in range(B):
+        # only what the tiles list (pruned lists leave unwritten slots between them), and final_idx only on the pixels of
+        # tiles with entries (the planar raster writes it for those alone: the backward skips empty tiles)
+        bins = plain["tile_bins"][b]
+        listed = torch.cat([torch.arange(s, e) for s, e in bins.tolist()]).cuda()
+        assert torch.equal(inst["sorted_ids"][b, listed], plain["sorted_ids"][b, listed])
+        busy = (bins[:, 1] > bins[:, 0]).reshape((H + 15) // 16, (W + 15) // 16)
+        busy = busy.repeat_interleave(16, 0).repeat_interleave(16, 1)[:H, :W]
+        assert torch.equal(inst["final_idx"][b][busy], plain["final_idx"][b][busy])
+    for k in ("radii", "render", "alpha", "depth_norm") + (("l1_loss",) if with_l1 else ()):
+        assert torch.equal(inst[k], plain[k]), k
+    assert float(plain["alpha"].max()) > 0.5 and int((plain["radii"] > 0).sum()) > N
+    for i, (a, b) in enumerate(zip(g1, g0)):
+        assert float(b.abs().max()) > 0 and rel_l2(a, b) < TIGHT, (i, rel_l2(a, b))
