@@ -250,6 +250,21 @@ def _abi_rasterize_bwd(*, B, N, img_h, img_w, planar, tile_bins, sorted_ids, cap
               c_int(v_sign_mask_c), _p(v_img_scale), c_float(v_img_scale_mul), c_int(pixels_per_lane), stream_ptr())
 
 
+def _abi_rasterize_nd_fwd(*, B, N, C, img_h, img_w, tile_bins, sorted_ids, capacity, records, colors, background, out_img,
+                          final_Ts, final_idx, pixels_per_lane=0):
+    _lib.call("gol_rasterize_nd_fwd", c_int(B), c_int(N), c_int(C), c_int(img_h), c_int(img_w), c_int(BLOCK),
+              _p(tile_bins, _I32), _p(sorted_ids, _I32), c_i64(capacity), _p(records), _p(colors), _p(background),
+              _p(out_img), _p(final_Ts), _p(final_idx, _I32), c_int(pixels_per_lane), stream_ptr())
+
+
+def _abi_rasterize_nd_bwd(*, B, N, C, img_h, img_w, tile_bins, sorted_ids, capacity, records, colors, background, final_Ts,
+                          final_idx, v_out_img, v_out_alpha=None, v_xy, v_conic, v_colors, v_opacity):
+    _lib.call("gol_rasterize_nd_bwd", c_int(B), c_int(N), c_int(C), c_int(img_h), c_int(img_w), c_int(BLOCK),
+              _p(tile_bins, _I32), _p(sorted_ids, _I32), c_i64(capacity), _p(records), _p(colors), _p(background),
+              _p(final_Ts), _p(final_idx, _I32), _p(v_out_img), _p(v_out_alpha), _p(v_xy), _p(v_conic), _p(v_colors),
+              _p(v_opacity), stream_ptr())
+
+
 def _bin_sort(B, N, xys, depths, radii, img_h, img_w, ws, conics=None, opacities=None):
     """conics + opacities given -> (Gaussian, tile) pairs that cannot reach alpha >= 1/255 are pruned
     (output-preserving); omitted -> gsplat's exact 3-sigma tile lists."""
@@ -276,7 +291,8 @@ def _project_fwd(B, N, means, scales, glob_scale, quats, viewmats, intrins, img_
 
 
 def _pack_records(B, N, xys, conics, colors, extra, opacities):
-    """gol_splat_pack: the rasterizer's packed records from gsplat-style attribute arrays."""
+    """gol_splat_pack: the rasterizer's packed records from gsplat-style attribute arrays (colors None: r = g = b = 0, the
+    records of the N-channel rasterizer)."""
     records = torch.empty(B, N, SPLAT_RECORD, dtype=torch.float32, device=xys.device)
     _lib.call("gol_splat_pack", c_int(B), c_int(N), fptr(xys), fptr(conics), fptr(colors), fptr(extra), fptr(opacities),
               fptr(records), stream_ptr())
@@ -346,7 +362,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, opacity, img_height, img_width,
                 block_width, background, return_alpha):
         dev = xys.device
-        N = xys.shape[0]
+        N, C = xys.shape[0], colors.shape[-1]
         xys, depths, conics, colors = _f32c(xys), _f32c(depths), _f32c(conics), _f32c(colors)
         opacity = _f32c(opacity).reshape(-1)
         radii = radii.to(torch.int32).contiguous()
@@ -357,21 +373,27 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.dims = (img_height, img_width)
         if n_isect < 1:
             # background-only image and final_T = 0 (alpha = 1)
-            out_img = torch.ones(img_height, img_width, 3, device=dev) * background
+            out_img = torch.ones(img_height, img_width, C, device=dev) * background
             final_Ts = torch.zeros(img_height, img_width, device=dev)
             ctx.save_for_backward(xys, conics, colors, opacity, background)
         else:
             T = _tiles(img_height, img_width)
             ws = _Workspace(1, N, T, n_isect, dev)
-            out_img = torch.empty(1, img_height, img_width, 3, device=dev)
+            out_img = torch.empty(1, img_height, img_width, C, device=dev)
             final_Ts = torch.empty(1, img_height, img_width, device=dev)
             final_idx = torch.empty(1, img_height, img_width, dtype=torch.int32, device=dev)
             with _lib.device_guard(dev):
                 _bin_sort(1, N, xys, depths, radii, img_height, img_width, ws, conics, opacity)
-                records = _pack_records(1, N, xys, conics, colors, None, opacity)
-                _abi_rasterize_fwd(B=1, N=N, img_h=img_height, img_w=img_width, planar=0, tile_bins=ws.tile_bins,
-                                   sorted_ids=ws.sorted_ids, capacity=ws.capacity, records=records, with_extra=0,
-                                   background=background, out_img=out_img, final_Ts=final_Ts, final_idx=final_idx)
+                if C == 3:
+                    records = _pack_records(1, N, xys, conics, colors, None, opacity)
+                    _abi_rasterize_fwd(B=1, N=N, img_h=img_height, img_w=img_width, planar=0, tile_bins=ws.tile_bins,
+                                       sorted_ids=ws.sorted_ids, capacity=ws.capacity, records=records, with_extra=0,
+                                       background=background, out_img=out_img, final_Ts=final_Ts, final_idx=final_idx)
+                else:   # gsplat's nd_rasterize_forward: geometry records without colour, colours as they are
+                    records = _pack_records(1, N, xys, conics, None, None, opacity)
+                    _abi_rasterize_nd_fwd(B=1, N=N, C=C, img_h=img_height, img_w=img_width, tile_bins=ws.tile_bins,
+                                          sorted_ids=ws.sorted_ids, capacity=ws.capacity, records=records, colors=colors,
+                                          background=background, out_img=out_img, final_Ts=final_Ts, final_idx=final_idx)
             ctx.ws = ws
             ctx.save_for_backward(xys, conics, colors, opacity, background, final_Ts, final_idx, records)
             out_img, final_Ts = out_img[0], final_Ts[0]
@@ -395,10 +417,17 @@ class _RasterizeGaussians(torch.autograd.Function):
             va = None if v_out_alpha is None else _f32c(v_out_alpha)
             vo = _f32c(v_out_img)
             with _lib.device_guard(xys.device):
-                _abi_rasterize_bwd(B=1, N=N, img_h=H, img_w=W, planar=0, tile_bins=ws.tile_bins, sorted_ids=ws.sorted_ids,
-                                   capacity=ws.capacity, records=records, with_extra=0, background=background,
-                                   final_Ts=final_Ts, final_idx=final_idx, v_out_img=vo, v_out_alpha=va, v_xy=v_xy,
-                                   v_conic=v_conic, v_colors=v_colors, v_opacity=v_opacity)
+                if colors.shape[-1] == 3:
+                    _abi_rasterize_bwd(B=1, N=N, img_h=H, img_w=W, planar=0, tile_bins=ws.tile_bins,
+                                       sorted_ids=ws.sorted_ids, capacity=ws.capacity, records=records, with_extra=0,
+                                       background=background, final_Ts=final_Ts, final_idx=final_idx, v_out_img=vo,
+                                       v_out_alpha=va, v_xy=v_xy, v_conic=v_conic, v_colors=v_colors, v_opacity=v_opacity)
+                else:
+                    _abi_rasterize_nd_bwd(B=1, N=N, C=colors.shape[-1], img_h=H, img_w=W, tile_bins=ws.tile_bins,
+                                          sorted_ids=ws.sorted_ids, capacity=ws.capacity, records=records, colors=colors,
+                                          background=background, final_Ts=final_Ts, final_idx=final_idx, v_out_img=vo,
+                                          v_out_alpha=va, v_xy=v_xy, v_conic=v_conic, v_colors=v_colors,
+                                          v_opacity=v_opacity)
         # ctx.ws stays: a second backward through this node (retain_graph=True, per-loss backward calls) needs the tile
         # lists again; autograd frees them with the graph
         return (v_xy, None, None, v_conic, None, v_colors, v_opacity[:, None]) + (None,) * 5
@@ -406,8 +435,10 @@ class _RasterizeGaussians(torch.autograd.Function):
 
 def rasterize_gaussians(xys, depths, radii, conics, num_tiles_hit, colors, opacity, img_height, img_width,
                         block_width, background=None, return_alpha=False):
-    """gsplat.rasterize_gaussians (0.1.11).  Only the 3-channel specialisation exists here: the
-    reference never calls the N-D variant (render_gsplat.py:65-104 passes 3-channel colours)."""
+    """gsplat.rasterize_gaussians (0.1.11): colors[N, C] for any C >= 1 (uint8 colours are divided by 255), background[C]
+    (None: ones), returns out_img[H, W, C] (and alpha[H, W] with return_alpha); gradients flow to xys, conics, colors and
+    opacity.  C == 3 runs the 3-channel kernels (gol_rasterize_fwd / _bwd, what the reference calls,
+    render_gsplat.py:65-104), every other C the N-channel ones (gol_rasterize_nd_fwd / _bwd, gsplat's nd_rasterize_*)."""
     assert block_width > 1 and block_width <= 16, "block_width must be between 2 and 16"
     if block_width != BLOCK:
         raise NotImplementedError("goliath_amd implements block_width=16 (the reference's value)")
@@ -417,8 +448,6 @@ def rasterize_gaussians(xys, depths, radii, conics, num_tiles_hit, colors, opaci
         raise ValueError("xys must have dimensions (N, 2)")
     if colors.ndimension() != 2:
         raise ValueError("colors must have dimensions (N, D)")
-    if colors.shape[-1] != 3:
-        raise NotImplementedError("only 3-channel colours are implemented (no N-D call site in the reference)")
     if background is not None:
         assert background.shape[0] == colors.shape[-1], "incorrect shape of background color tensor"
     else:

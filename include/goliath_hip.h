@@ -130,7 +130,8 @@ int gol_bin_sort(int B, int N, const float* xys, const float* depths, const int3
  *   [0] x [1] y [2] a' [3] b' | [4] c' [5] opacity [6] r [7] g | [8] b [9] extra [10] tau [11] 1/a | [12] 1/c [13] exact [14-15] pad
  *   (a', b', c' = the conic scaled for the pixel loops, tau / 1/a / 1/c / exact = the per-Gaussian part of the
  *   alpha >= 1/255 reach test; goliath_amd/csrc/gol_common.h) written by gol_project_fwd (fused path) or by
- *   gol_splat_pack from xys[B,N,2], conics[B,N,3], colors[B,N,3], extra[B,N] (NULL = 0), opacities[B,N] (the
+ *   gol_splat_pack from xys[B,N,2], conics[B,N,3], colors[B,N,3] (NULL = 0: records for gol_rasterize_nd_*, which
+ *   stage their colours separately), extra[B,N] (NULL = 0), opacities[B,N] (the
  *   gsplat-compatible operators): a list entry costs one aligned 64-byte fetch instead of up to five sectors of five arrays.
  * One launch composites the colour and, with with_extra != 0, the 4th channel "extra" of the records
  * (the depth pass of render_gsplat.py:91-104 fused into the colour pass; its background is 0).
@@ -196,6 +197,29 @@ int gol_raster_count_pairs(int B, int N, int img_h, int img_w, const int32_t* ti
                            int64_t capacity, const float* records, const int32_t* final_idx, uint64_t* counts, void* stream);
 /* What pixels_per_lane = 0 means for the forward of a launch of B views (1 for B <= 2, else 2). */
 int gol_raster_plan(int B, int* fwd_pixels_per_lane);
+
+/* ------------------------------------------------------------------------------------------
+ * N-channel tile rasterizer.  Replaces gsplat: nd_rasterize_forward / nd_rasterize_backward (what rasterize_gaussians
+ * runs for colors[N, C], C != 3; semantics SURVEY.md A.3, A.4 -- the same alpha caps, cuts and stopping rule as
+ * gol_rasterize_fwd / _bwd, which it equals channel by channel for C = 3).  gsplat's layouts, any C >= 1:
+ *   records[B,N,GOL_SPLAT_RECORD] as for gol_rasterize_fwd (only the geometry is read: gol_splat_pack with colors = NULL
+ *   fills them); colors[B,N,C] dense, interleaved; background[C]; out_img / v_out_img [B,H,W,C]; final_Ts[B,H,W];
+ *   final_idx[B,H,W] int32 = gsplat's (index into the view's sorted_ids segment of the last contributing Gaussian,
+ *   0 if none); tile_bins / sorted_ids / capacity from gol_bin_sort.  H * W * C * 4 bytes per view must stay < 4 GiB.
+ * fwd OVERWRITES out_img, final_Ts, final_idx.  pixels_per_lane as for gol_rasterize_fwd (0 = gol_raster_plan(B)).
+ * bwd ACCUMULATES into v_xy[B,N,2] v_conic[B,N,3] v_colors[B,N,C] v_opacity[B,N] (dense arrays; the caller zeroes them);
+ *   v_out_img is required, v_out_alpha[B,H,W] may be NULL (= 0).
+ * Channels are processed in chunks of at most 16; C > 16 walks each tile list once per chunk.
+ * ---------------------------------------------------------------------------------------- */
+int gol_rasterize_nd_fwd(int B, int N, int C, int img_h, int img_w, int block, const int32_t* tile_bins,
+                         const int32_t* sorted_ids, int64_t capacity, const float* records, const float* colors,
+                         const float* background, float* out_img, float* final_Ts, int32_t* final_idx,
+                         int pixels_per_lane, void* stream);
+int gol_rasterize_nd_bwd(int B, int N, int C, int img_h, int img_w, int block, const int32_t* tile_bins,
+                         const int32_t* sorted_ids, int64_t capacity, const float* records, const float* colors,
+                         const float* background, const float* final_Ts, const int32_t* final_idx,
+                         const float* v_out_img, const float* v_out_alpha, float* v_xy, float* v_conic,
+                         float* v_colors, float* v_opacity, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * One render direction of a batch of views as ONE call (csrc/render.hip): what AutoEncoder.render issues per view from
