@@ -119,7 +119,16 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False):
     if urhand_module is None:
         import ca_code.models.urhand as urhand_module
     urhand_module.get_shadow_map = shadowmap.get_shadow_map
-    if mesh_render_layer:
+    if isinstance(mesh_render_layer, str) and mesh_render_layer == "fused":
+        import warnings
+
+        warnings.warn("patch_urhand(mesh_render_layer='fused'): the model's final, differentiable render goes through "
+                      "goliath_amd.meshraster.FusedRenderLayer (RenderLayer's numbers on fused HIP kernels), whose edge "
+                      "gradients are checked against finite differences only -- drtk is absent in this build, so their parity "
+                      "with drtk.edge_grad_estimator is UNVERIFIED; meshraster.EDGE_STATS (opt-in: GOLIATH_EDGE_STATS=1) counts "
+                      "the discontinuities that receive no gradient", RuntimeWarning, stacklevel=2)
+        urhand_module.RenderLayer = meshraster.FusedRenderLayer
+    elif mesh_render_layer:
         import warnings
 
         warnings.warn("patch_urhand(mesh_render_layer=True): the model's final, differentiable render goes through "

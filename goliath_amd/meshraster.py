@@ -237,3 +237,130 @@ class RenderLayer(torch.nn.Module):
             img = edge_grad_estimator(v_pix, self.vi, bary_img, img, index_img, depth_img)
         return {"render": img, "depth_img": depth_img, "v_pix": v_pix, "vt_img": vt_img, "index_img": index_img,
                 "bary_img": bary_img, "mask": mask}
+
+
+# ---- fused HIP textured render (csrc/meshrender.hip) ---------------------------------------------------------------------
+# One marshaller per C-ABI entry (keywords = the header's parameter names; a pointer is a GPU tensor, checked, a device
+# address or None; stream = the current one).
+_F32, _I32 = torch.float32, torch.int32
+
+
+def _p(x, dtype=_F32, name="tensor"):
+    return ctypes.c_void_p(x) if x is None or isinstance(x, int) else _lib.ptr(x, dtype, name)
+
+
+def _abi_mesh_render_fwd(*, B, F, Vt, C, H, W, Ht, Wt, vt, vti, tex, index_img, bary_img, vt_img, render, mask):
+    _lib.call("gol_mesh_render_fwd", c_int(B), c_int(F), c_int(Vt), c_int(C), c_int(H), c_int(W), c_int(Ht), c_int(Wt),
+              _p(vt), _p(vti, _I32), _p(tex), _p(index_img, _I32), _p(bary_img), _p(vt_img), _p(render), _p(mask),
+              stream_ptr())
+
+
+def _abi_mesh_render_bwd(*, B, V, F, Vt, C, H, W, Ht, Wt, v_pix, vi, vt, vti, tex, index_img, bary_img, g_render=None,
+                         g_vt_img=None, g_bary_img=None, g_depth_img=None, g_tex=None, g_v_pix=None):
+    _lib.call("gol_mesh_render_bwd", c_int(B), c_int(V), c_int(F), c_int(Vt), c_int(C), c_int(H), c_int(W), c_int(Ht),
+              c_int(Wt), _p(v_pix), _p(vi, _I32), _p(vt), _p(vti, _I32), _p(tex), _p(index_img, _I32), _p(bary_img),
+              _p(g_render), _p(g_vt_img), _p(g_bary_img), _p(g_depth_img), _p(g_tex), _p(g_v_pix), stream_ptr())
+
+
+def _abi_mesh_render_edge_bwd(*, B, V, F, C, H, W, v_pix, vi, index_img, depth_img, render, g_render, g_v_pix,
+                              edge_stats=None):
+    _lib.call("gol_mesh_render_edge_bwd", c_int(B), c_int(V), c_int(F), c_int(C), c_int(H), c_int(W), _p(v_pix),
+              _p(vi, _I32), _p(index_img, _I32), _p(depth_img), _p(render), _p(g_render), _p(g_v_pix),
+              _p(edge_stats, _I32), stream_ptr())
+
+
+def _f32(t):
+    return None if t is None else t.detach().to(torch.float32).contiguous()
+
+
+class _RenderTextured(torch.autograd.Function):
+    """render_textured's forward and backward on the HIP kernels (no host sync: graph-capturable)."""
+
+    @staticmethod
+    def forward(ctx, v_pix, vi, vt, vti, tex, index_img, depth_img, bary_img, edge_grad):
+        B, H, W = index_img.shape
+        C, Ht, Wt = tex.shape[1:]
+        dev = v_pix.device
+        vi32, vti32 = vi.to(torch.int32).contiguous(), vti.to(torch.int32).contiguous()
+        vt32, tex32 = _f32(vt), _f32(tex)
+        idx32, depth32, bary32 = index_img.to(torch.int32).contiguous(), _f32(depth_img), _f32(bary_img)
+        vt_img = torch.empty(B, 2, H, W, device=dev)
+        render = torch.empty(B, C, H, W, device=dev)
+        mask = torch.empty(B, 1, H, W, device=dev)
+        with _lib.device_guard(dev):
+            _abi_mesh_render_fwd(B=B, F=vti32.shape[0], Vt=vt32.shape[0], C=C, H=H, W=W, Ht=Ht, Wt=Wt, vt=vt32, vti=vti32,
+                                 tex=tex32, index_img=idx32, bary_img=bary32, vt_img=vt_img, render=render, mask=mask)
+        ctx.save_for_backward(_f32(v_pix), vi32, vt32, vti32, tex32, idx32, depth32, bary32, render)
+        ctx.edge_grad = bool(edge_grad)
+        ctx.dtypes = (v_pix.dtype, tex.dtype)
+        ctx.mark_non_differentiable(mask)
+        # depth / barycentrics pass through unchanged: the backward chains their gradients into v_pix
+        return render, vt_img, depth_img.view_as(depth_img), bary_img.view_as(bary_img), mask
+
+    @staticmethod
+    def backward(ctx, g_render, g_vt_img, g_depth_img, g_bary_img, _g_mask):
+        v_pix, vi, vt, vti, tex, index_img, depth_img, bary_img, render = ctx.saved_tensors
+        need_v, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[4]
+        g_v = torch.zeros_like(v_pix) if need_v else None
+        g_t = torch.zeros_like(tex) if need_t else None
+        g_render, g_vt_img, g_depth_img, g_bary_img = (_f32(g) for g in (g_render, g_vt_img, g_depth_img, g_bary_img))
+        B, H, W = index_img.shape
+        C, Ht, Wt = tex.shape[1:]
+        V, F = v_pix.shape[1], vi.shape[0]
+        with _lib.device_guard(v_pix.device):
+            if need_v or need_t:
+                _abi_mesh_render_bwd(B=B, V=V, F=F, Vt=vt.shape[0], C=C, H=H, W=W, Ht=Ht, Wt=Wt, v_pix=v_pix, vi=vi, vt=vt,
+                                     vti=vti, tex=tex, index_img=index_img, bary_img=bary_img, g_render=g_render,
+                                     g_vt_img=g_vt_img if need_v else None, g_bary_img=g_bary_img if need_v else None,
+                                     g_depth_img=g_depth_img if need_v else None, g_tex=g_t, g_v_pix=g_v)
+            if need_v and ctx.edge_grad and g_render is not None:
+                stats = torch.zeros(2, dtype=torch.int32, device=v_pix.device) if COLLECT_EDGE_STATS else None
+                _abi_mesh_render_edge_bwd(B=B, V=V, F=F, C=C, H=H, W=W, v_pix=v_pix, vi=vi, index_img=index_img,
+                                          depth_img=depth_img, render=render, g_render=g_render, g_v_pix=g_v,
+                                          edge_stats=stats)
+                if stats is not None:   # _EdgeGrad's counters, same meaning, on the device
+                    st = EDGE_STATS.setdefault(v_pix.device, {"edges": None, "dropped": None})
+                    n_e, n_d = stats[0].long(), stats[1].long()
+                    st["edges"] = n_e if st["edges"] is None else st["edges"] + n_e
+                    st["dropped"] = n_d if st["dropped"] is None else st["dropped"] + n_d
+        g_v = None if g_v is None else g_v.to(ctx.dtypes[0])
+        g_t = None if g_t is None else g_t.to(ctx.dtypes[1])
+        return g_v, None, None, None, g_t, None, None, None, None
+
+
+def render_textured(v_pix, vi, vt, vti, tex, index_img, depth_img, bary_img, edge_grad=False):
+    """RenderLayer's textured render after the rasterizer as ONE fused HIP op (csrc/meshrender.hip).
+
+    v_pix[B,V,3], vi[F,3], vt[Vt,2] (uv in [0, 1]), vti[F,3], tex[B,C,Ht,Wt]; index_img[B,H,W], depth_img[B,H,W] and
+    bary_img[B,3,H,W] as `rasterize` returns them.  Returns (render[B,C,H,W], vt_img[B,2,H,W], depth_img, bary_img,
+    mask[B,1,H,W]) with RenderLayer's values: render = grid_sample(tex, vt_img, bilinear, align_corners=False, zero
+    padding) * mask.  Differentiable outputs: render, vt_img, depth_img and bary_img; gradients go to tex and to v_pix
+    (through the function `render()` evaluates, visibility fixed) and, with edge_grad, v_pix also receives `_EdgeGrad`'s
+    discontinuity term.  vi, vt, vti and the images get none.  Every tensor must be on the GPU: there is no CPU path."""
+    for name, t in (("v_pix", v_pix), ("vi", vi), ("vt", vt), ("vti", vti), ("tex", tex), ("index_img", index_img),
+                    ("depth_img", depth_img), ("bary_img", bary_img)):
+        if not t.is_cuda:
+            raise _lib.GoliathHipError(f"render_textured: {name} must be a CUDA(HIP) tensor; there is no CPU path")
+    if tex.shape[0] != v_pix.shape[0] or index_img.shape[0] != v_pix.shape[0]:
+        raise _lib.GoliathHipError("render_textured: v_pix, tex and the images need the same batch size")
+    return _RenderTextured.apply(v_pix, vi, vt, vti, tex, index_img, depth_img, bary_img, edge_grad)
+
+
+class FusedRenderLayer(RenderLayer):
+    """RenderLayer (same constructor, forward arguments and output dict) with everything after the rasterizer in one fused
+    HIP forward and backward (`render_textured`): no [B,H,W,3,3] gathers and no host sync in the backward, so a training
+    step through it can be captured as a graph.  Its numbers are RenderLayer's up to fp32 arithmetic and float-atomic
+    order; EDGE_STATS counts with the same meaning."""
+
+    def forward(self, verts: torch.Tensor, tex: torch.Tensor, K: torch.Tensor, Rt: torch.Tensor,
+                background: Optional[torch.Tensor] = None, output_filters: Optional[List[str]] = None,
+                edge_grad: bool = True):
+        assert output_filters is None
+        assert background is None
+        v_pix = transform(verts, K=K, Rt=Rt)
+        index_img, depth_img, bary_img = rasterize(v_pix, self.vi, self.h, self.w)
+        need_vert_grad = torch.is_grad_enabled() and v_pix.requires_grad
+        img, vt_img, depth_img, bary_img, mask = render_textured(v_pix, self.vi, self.vt, self.vti, tex, index_img,
+                                                                 depth_img, bary_img, edge_grad=edge_grad and need_vert_grad)
+        return {"render": img, "depth_img": depth_img, "v_pix": v_pix, "vt_img": vt_img, "index_img": index_img,
+                "bary_img": bary_img, "mask": mask}

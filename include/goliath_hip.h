@@ -588,6 +588,39 @@ int64_t gol_mesh_raster_workspace_bytes(int B, int F);
 int gol_mesh_raster(int B, int V, int F, int H, int W, const float* v_pix, const int32_t* vi, int32_t* index_img,
                     float* depth_img, float* bary_img, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Textured mesh render after gol_mesh_raster, forward and backward: the rest of the reference's drtk layer
+ * (ca_code/utils/render_drtk.py:44-70: drtk.render's differentiable depth / barycentrics, drtk.interpolate of the uv,
+ * grid_sample of the texture, drtk.edge_grad_estimator), as goliath_amd.meshraster.RenderLayer composes it in PyTorch.
+ *   v_pix[B,V,3], vi[F,3] int32 as for gol_mesh_raster; vt[Vt,2] uv in [0,1], vti[F,3] int32 uv ids; tex[B,C,Ht,Wt]
+ *   (planar, any C >= 1); index_img[B,H,W] int32, depth_img[B,H,W], bary_img[B,3,H,W] as gol_mesh_raster wrote them.
+ *   A pixel whose face or uv / vertex ids are out of range counts as empty.
+ * fwd writes (every element) vt_img[B,2,H,W] = sum_k bary_k (2 vt[vti[f,k]] - 1), render[B,C,H,W] =
+ *   grid_sample(tex, vt_img, bilinear, align_corners=False, zero padding) * mask, mask[B,1,H,W] = (index >= 0); 0 where empty.
+ * bwd ACCUMULATES (caller zeroes) g_tex[B,C,Ht,Wt] (NULL = not wanted) and g_v_pix[B,V,3] (NULL = not wanted): from
+ *   g_render[B,C,H,W] and the optional g_vt_img[B,2,H,W], g_bary_img[B,3,H,W], g_depth_img[B,H,W] (NULL = zero), chained
+ *   through the perspective-correct barycentrics of the pixel's face re-evaluated from v_pix (anchored at the face's first
+ *   vertex, sampled at (j + 0.5, i + 0.5), w_k = b_k / z_k, bary = w / sum w, depth = 1 / sum w: all nine coordinates).
+ *   v_pix is needed when g_v_pix is given.  Visibility (index_img) is held fixed.
+ * edge_bwd ACCUMULATES into g_v_pix the discontinuity term of meshraster._EdgeGrad (right / lower neighbour pairs whose
+ *   faces differ and share no mesh edge; occluder = nearer face, empty = +inf; its edge crossing the pair's segment
+ *   nearest to the middle, within one pixel; coefficient sum_c (g_p + g_q) (img_p - img_q) / 2 times d_ac^2 /
+ *   (d_ac^2 + d_al^2), chained into the edge's two endpoints' image coordinates; nothing to z).  render = the forward's
+ *   render, g_render its upstream gradient.  edge_stats (int32[2], may be NULL) ACCUMULATES {pairs kept, pairs without a
+ *   crossing within a pixel}.
+ * No workspace.  Float-atomic order makes g_tex and g_v_pix nondeterministic in the last bits.
+ * ---------------------------------------------------------------------------------------- */
+int gol_mesh_render_fwd(int B, int F, int Vt, int C, int H, int W, int Ht, int Wt, const float* vt, const int32_t* vti,
+                        const float* tex, const int32_t* index_img, const float* bary_img, float* vt_img, float* render,
+                        float* mask, void* stream);
+int gol_mesh_render_bwd(int B, int V, int F, int Vt, int C, int H, int W, int Ht, int Wt, const float* v_pix,
+                        const int32_t* vi, const float* vt, const int32_t* vti, const float* tex, const int32_t* index_img,
+                        const float* bary_img, const float* g_render, const float* g_vt_img, const float* g_bary_img,
+                        const float* g_depth_img, float* g_tex, float* g_v_pix, void* stream);
+int gol_mesh_render_edge_bwd(int B, int V, int F, int C, int H, int W, const float* v_pix, const int32_t* vi,
+                             const int32_t* index_img, const float* depth_img, const float* render,
+                             const float* g_render, float* g_v_pix, int32_t* edge_stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
