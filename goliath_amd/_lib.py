@@ -25,6 +25,8 @@ _SYMBOLS = [
     "gol_tail_conv_fwd", "gol_tail_conv_bwd", "gol_tail_conv_bwd_scratch_floats", "gol_ssim_blocks", "gol_ssim_fwd", "gol_ssim_bwd",
     "gol_shadow_pcf", "gol_imgtail_partial_floats", "gol_imgtail_fwd", "gol_imgtail_bwd", "gol_mvp_shadow_march", "gol_mesh_raster_workspace_bytes", "gol_mesh_raster",
     "gol_mesh_render_fwd", "gol_mesh_render_bwd", "gol_mesh_render_edge_bwd",
+    "gol_vert_normals_fwd", "gol_vert_normals_bwd", "gol_values_to_uv_fwd", "gol_values_to_uv_bwd", "gol_uvgeom_fwd",
+    "gol_uvgeom_bwd",
 ]
 
 

@@ -4,6 +4,7 @@
     dropin.install()              # before importing ca_code.* / extensions.*
     dropin.patch_rgca()           # optional: fused shading tail + batched, sync-free render
     dropin.patch_light_decorator()  # optional: the env-relight driver hands over ONE shared pyramid (config 2)
+    dropin.patch_geometry()       # optional: GeometryModule.to_uv / .vn and the decoder's postex / tn on the uvgeom kernels
 
 `install()` registers the module names the reference imports for its native code:
     gsplat            project_gaussians, rasterize_gaussians   (ca_code/utils/render_gsplat.py:10-11)
@@ -47,6 +48,21 @@ def patch_rgca(rgca_module=None):
     rgca_module.AutoEncoder.forward = fused.autoencoder_forward
     rgca_module.PrimDecoder.forward = fused.prim_decoder_forward
     return rgca_module
+
+
+def patch_geometry(geom_module=None):
+    """Rebind `GeometryModule.to_uv` and `.vn` (ca_code/utils/geom.py:267-271) to the fused HIP operators of
+    goliath_amd.uvgeom (gol_values_to_uv / gol_vert_normals: no boolean-mask gather, no host sync, graph-capturable).  The
+    packed topology is built lazily from the module's own `vi` / `index_image` / `bary_image` buffers and rebuilt when
+    their device or shape changes.  With it, goliath_amd.rgca.prim_decoder_forward makes one `uv_geometry` call for
+    `postex` / `tn`.  Idempotent.  Returns the patched module."""
+    from . import uvgeom
+
+    if geom_module is None:
+        import ca_code.utils.geom as geom_module
+    geom_module.GeometryModule.to_uv = uvgeom.geometry_to_uv
+    geom_module.GeometryModule.vn = uvgeom.geometry_vn
+    return geom_module
 
 
 def _shared_mipmap(self, bsize, device, scale=1.0):

@@ -17,6 +17,7 @@ import os
 from .render_gs import render_batch
 from .shade import shading_tail
 from .tail import fused_tail
+from .uvgeom import fused_topology, uv_geometry
 from .views import ViewSet
 
 
@@ -157,9 +158,13 @@ def prim_decoder_forward(self, embs: th.Tensor, geom: th.Tensor, headrel_campos:
                          n_lights: th.Tensor, preconv_envmap: Optional[th.Tensor] = None,
                          lightrot: Optional[th.Tensor] = None):
     B = embs.shape[0]
-    # uv position / normal maps and the two decoders: unchanged PyTorch (rgca.py:483-503)
-    postex = self.geo_fn.to_uv(geom)
-    tn = F.normalize(self.geo_fn.to_uv(self.geo_fn.vn(geom)), dim=1)
+    # uv position / normal maps (rgca.py:483-491) and the two decoders (unchanged PyTorch, :493-503)
+    topo = fused_topology(self.geo_fn, geom.shape[1])
+    if topo is not None:  # opt-in (dropin.patch_geometry / geo_fn.uv_topology): both maps from ONE fused HIP call
+        postex, tn = uv_geometry(geom, topo, norm_eps=1e-12)
+    else:
+        postex = self.geo_fn.to_uv(geom)
+        tn = F.normalize(self.geo_fn.to_uv(self.geo_fn.vn(geom)), dim=1)
     z = self.encmod(embs).view(-1, 256, 8, 8)
     view = self.viewmod(F.normalize(headrel_campos, dim=1))[:, :, None, None].expand(-1, -1, 8, 8)
     zv = th.cat([z, view], dim=1)

@@ -621,6 +621,48 @@ int gol_mesh_render_edge_bwd(int B, int V, int F, int C, int H, int W, const flo
                              const int32_t* index_img, const float* depth_img, const float* render,
                              const float* g_render, float* g_v_pix, int32_t* edge_stats, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * uvgeom: tracked mesh -> UV position / normal maps, forward and backward (csrc/uvgeom.hip).  Replaces the reference's
+ * per-step PyTorch of ca_code/utils/geom.py:308-346 (values_to_uv, face_normals, vert_normals) as called by
+ * PrimDecoder.forward (ca_code/models/rgca.py:483-491), ConvTeacherDecoder.forward (ca_code/models/urhand.py:375-394, 447)
+ * and hand_mvp.py:231-236, 394.  The topology arrays are packed once by goliath_amd.uvgeom.UVTopology (all int32):
+ *   vi[F,3]; vf_start[V+1], vf_slot[3F]: vertex -> (face, corner) slots, slot = 3 face + corner, ascending per vertex;
+ *   texel_rec[S*S,4]: triple id (-1 = uncovered, geom.py:310) and the bit patterns of the texel's three barycentrics;
+ *   triples[T,3]: the distinct vertex triples; item_start[I+1], item_tid[I], texel_of[M]: the covered texels grouped by
+ *   triple, every triple's run cut into items of at most 64 texels; vt_start[V+1], vt_slot[3I]: vertex -> (item, corner)
+ *   slots, slot = 3 item + corner.  Ids out of range count as absent (uncovered texel, skipped face).
+ * gol_vert_normals_fwd: vert_normals(verts, vi, eps) (geom.py:337-346): vn[B,V,3] = s / max(|s|, eps), s = the sum over
+ *   the vertex's faces of cross / max(|cross|, 1e-5) (geom.py:327-334), summed in face order.
+ * gol_vert_normals_bwd: g_vn[B,V,3] -> g_verts[B,V,3] (every element written); g_s[B,V,3] is scratch.
+ * gol_values_to_uv_fwd: values_to_uv (geom.py:308-324) for values[B,V,C], any C >= 1: out[B,C,S,S], every element
+ *   written, 0 where uncovered.
+ * gol_values_to_uv_bwd: g_out[B,C,S,S] -> g_values[B,V,C] (every element written); item_sums[B,I,3,C] is scratch.
+ * gol_uvgeom_fwd: the pair of rgca.py:483-491 in one call: vn[B,V,3] as gol_vert_normals_fwd(eps = vn_eps) writes it
+ *   (kept by the caller for the backward), postex[B,3,S,S] = to_uv(verts), tn[B,3,S,S] = x / max(|x|, norm_eps) with
+ *   x = to_uv(vn) (F.normalize over the channels: norm_eps = 1e-12; urhand.py:394 uses 1e-5).
+ * gol_uvgeom_bwd: g_postex, g_tn [B,3,S,S] (NULL = zero) -> g_verts[B,V,3] (every element written);
+ *   item_sums[B,I,18] and g_s[B,V,3] are scratch.
+ * A norm below its eps makes the denominator a constant in the derivative (autograd's clamp).  No atomics: every sum
+ * has a fixed order and all outputs are bitwise reproducible.
+ * ---------------------------------------------------------------------------------------- */
+int gol_vert_normals_fwd(int B, int V, int F, const float* verts, const int32_t* vi, const int32_t* vf_start,
+                         const int32_t* vf_slot, float eps, float* vn, void* stream);
+int gol_vert_normals_bwd(int B, int V, int F, const float* verts, const int32_t* vi, const int32_t* vf_start,
+                         const int32_t* vf_slot, float eps, const float* g_vn, float* g_s, float* g_verts, void* stream);
+int gol_values_to_uv_fwd(int B, int V, int C, int S, int T, const float* values, const int32_t* texel_rec,
+                         const int32_t* triples, float* out, void* stream);
+int gol_values_to_uv_bwd(int B, int V, int C, int S, int T, int I, const int32_t* texel_rec, const int32_t* item_start,
+                         const int32_t* texel_of, const int32_t* vt_start, const int32_t* vt_slot, const float* g_out,
+                         float* item_sums, float* g_values, void* stream);
+int gol_uvgeom_fwd(int B, int V, int F, int S, int T, const float* verts, const int32_t* vi, const int32_t* vf_start,
+                   const int32_t* vf_slot, const int32_t* texel_rec, const int32_t* triples, float vn_eps, float norm_eps,
+                   float* vn, float* postex, float* tn, void* stream);
+int gol_uvgeom_bwd(int B, int V, int F, int S, int T, int I, const float* verts, const int32_t* vi,
+                   const int32_t* vf_start, const int32_t* vf_slot, const int32_t* texel_rec, const int32_t* triples,
+                   const int32_t* item_start, const int32_t* item_tid, const int32_t* texel_of, const int32_t* vt_start,
+                   const int32_t* vt_slot, float vn_eps, float norm_eps, const float* vn, const float* g_postex,
+                   const float* g_tn, float* item_sums, float* g_s, float* g_verts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
