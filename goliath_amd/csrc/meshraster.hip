@@ -22,10 +22,18 @@
 namespace {
 
 struct FaceRec {
-  // barycentrics relative to vertex a (anchored form: the edge functions evaluated in absolute pixel coordinates lose
-  // ~1e-4 of their value to cancellation in a 1024^2 image -- 0.2 mm of depth at 1 m, visible in the shadow test
-  // exp(-(d1 - d2) / 8)):  b1 = e[3] (x - ax) + e[4] (y - ay),  b2 = e[6] (x - ax) + e[7] (y - ay),  b0 = 1 - b1 - b2;
-  // e[0], e[1] = (ax, ay); e[2], e[5], e[8] unused
+  // edge functions relative to vertex a (anchored form: evaluated in absolute pixel coordinates they lose ~1e-4 of their
+  // value to cancellation in a 1024^2 image -- 0.2 mm of depth at 1 m, visible in the shadow test exp(-(d1 - d2) / 8)),
+  // UN-NORMALISED and oriented so that inside is >= 0 for either winding:
+  //   E1 = e[3] (x - ax) + e[4] (y - ay),  E2 = e[6] (x - ax) + e[7] (y - ay),  E0 = e[2] - E1 - E2,  e[2] = |area|;
+  // coverage is decided on E0, E1, E2 and the barycentrics are b_k = E_k e[5], e[5] = 1 / |area|.  The coefficients are
+  // vertex differences (times a power of two).  While every coefficient x offset product fits fp32's 24 bits (vertices on a
+  // quarter-pixel grid, faces a few tens of pixels across: bits of the edge vector + bits of the offset <= 24) every
+  // product and sum above is exact, so a sample ON an edge gives exactly 0 in both faces that share it -- both cover it,
+  // none leaves a crack -- and an outline sample is covered as the rule says.  Beyond that (2^-8 grid with faces of 100
+  // pixels: ~40 bits) the products round, per face, and an on-edge sample may be rejected by both neighbours, as for any
+  // generic mesh within rounding of an edge.  (Coefficients divided by the area, as before, were rounded per face even on
+  // the coarse grid: two neighbours could both see -1e-8 on their common edge.)  e[0], e[1] = (ax, ay); e[8] unused
   float e[9];
   float iz[3];     // 1 / z of the three vertices
   int32_t tx0, tx1, ty0, ty1;  // inclusive tile bounds, tx1 < tx0 = culled
@@ -51,14 +59,22 @@ __global__ __launch_bounds__(256) void face_setup_kernel(int V, int F, int H, in
     const float ax = p[3 * i0], ay = p[3 * i0 + 1], az = p[3 * i0 + 2];
     const float bx = p[3 * i1], by = p[3 * i1 + 1], bz = p[3 * i1 + 2];
     const float cx = p[3 * i2], cy = p[3 * i2 + 1], cz = p[3 * i2 + 2];
-    const float area = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);
     const bool fin = isfinite(ax) && isfinite(ay) && isfinite(bx) && isfinite(by) && isfinite(cx) && isfinite(cy);
-    if (fin && az > 0.f && bz > 0.f && cz > 0.f && area != 0.f) {
-      const float ia = 1.f / area;
-      // barycentric of vertex b: area(p, c, a) / area, of vertex c: area(p, a, b) / area; both vanish at a
-      r.e[0] = ax; r.e[1] = ay; r.e[2] = 0.f;
-      r.e[3] = (cy - ay) * ia; r.e[4] = (ax - cx) * ia; r.e[5] = 0.f;
-      r.e[6] = (ay - by) * ia; r.e[7] = (bx - ax) * ia; r.e[8] = 0.f;
+    // the two edge vectors leaving a, one of them scaled by a power of two (exact) that brings the largest component to
+    // [0.5, 1): the signs of the edge functions do not change, and a face with vertices at 1e30 pixels neither overflows
+    // its area nor its edge functions (the exponent is clamped: above ~1e34 pixels the area does overflow and the face is
+    // skipped)
+    const float ux = bx - ax, uy = by - ay, wx = cx - ax, wy = cy - ay;
+    int ex = 0;
+    frexpf(fmaxf(fmaxf(fabsf(ux), fabsf(uy)), fmaxf(fabsf(wx), fabsf(wy))), &ex);
+    const float sc = ldexpf(1.f, -min(max(ex, -100), 100));
+    const float area = (ux * sc) * wy - (uy * sc) * wx;
+    if (fin && az > 0.f && bz > 0.f && cz > 0.f && area != 0.f && isfinite(area)) {
+      const float sg = area > 0.f ? sc : -sc;
+      // weight of vertex b: area(p, c, a), of vertex c: area(p, a, b) (both vanish at a), oriented and scaled like |area|
+      r.e[0] = ax; r.e[1] = ay; r.e[2] = fabsf(area);
+      r.e[3] = wy * sg; r.e[4] = -wx * sg; r.e[5] = 1.f / fabsf(area);
+      r.e[6] = -uy * sg; r.e[7] = ux * sg; r.e[8] = 0.f;
       r.iz[0] = 1.f / az; r.iz[1] = 1.f / bz; r.iz[2] = 1.f / cz;
       // pixels whose centre can be inside: centre x = j + 0.5 in [min, max]
       const float x0 = fminf(ax, fminf(bx, cx)), x1 = fmaxf(ax, fmaxf(bx, cx));
@@ -193,17 +209,17 @@ __global__ __launch_bounds__(256) void mesh_raster_kernel(int B, int F, int H, i
           const float4 r0 = src[0], r1 = src[1], r2 = src[2];  // e[0..8], iz[0..2]
           s_rec[0][tid] = make_float4(r0.x, r0.y, r0.w, r1.x);  // ax ay e3 e4
           s_rec[1][tid] = make_float4(r1.z, r1.w, r2.y, r2.z);  // e6 e7 iz0 iz1
-          s_rec[2][tid] = make_float4(r2.w, __int_as_float(s_face[c0 + tid]), 0.f, 0.f);  // iz2, face index
+          s_rec[2][tid] = make_float4(r2.w, __int_as_float(s_face[c0 + tid]), r0.z, r1.y);  // iz2, face index, |area|, 1 / |area|
         }
         __syncthreads();
         for (int k = 0; k < cn; ++k) {
           const float4 q0 = s_rec[0][k], q1 = s_rec[1][k], q2 = s_rec[2][k];  // same address in every lane: LDS broadcast
           const float dx = px - q0.x, dy = py - q0.y;
-          const float b1 = q0.z * dx + q0.w * dy;
-          const float b2 = q1.x * dx + q1.y * dy;
-          const float b0 = 1.f - b1 - b2;
-          if (b0 >= 0.f && b1 >= 0.f && b2 >= 0.f) {
-            const float w0 = b0 * q1.z, w1 = b1 * q1.w, w2 = b2 * q2.x;
+          const float E1 = q0.z * dx + q0.w * dy;
+          const float E2 = q1.x * dx + q1.y * dy;
+          const float E0 = q2.z - E1 - E2;
+          if (E0 >= 0.f && E1 >= 0.f && E2 >= 0.f) {
+            const float w0 = (E0 * q2.w) * q1.z, w1 = (E1 * q2.w) * q1.w, w2 = (E2 * q2.w) * q2.x;
             const float iz = w0 + w1 + w2;  // 1 / depth at the sample
             const int fi = __float_as_int(q2.y);
             if (iz > best_iz || (iz == best_iz && fi < best)) {  // nearer; exact ties go to the lower face index

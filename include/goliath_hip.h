@@ -580,6 +580,14 @@ int gol_imgtail_bwd(int B, int H, int W, const float* rgb, const float* alpha, c
  *   bary_img[B,3,H,W] (may be NULL): perspective-correct barycentrics of the sample.
  * Conventions (drtk's source is not in the reference tree): sample at the pixel centre (j + 0.5, i + 0.5); coverage =
  * all edge functions >= 0, either winding; faces with a vertex at z <= 0 are skipped; depth ties -> lower face index.
+ * Coverage is decided in fp32 on un-normalised edge functions anchored at the face's first vertex.  The decision is EXACT
+ * (a sample on a shared edge is covered by both neighbours, one on the outline is covered) only while every product of an
+ * edge-vector component of the face with a sample offset from its first vertex fits 24 bits: e.g. vertices on a
+ * quarter-pixel grid and faces a few tens of pixels across.  Outside that range (finer grids, larger faces, any generic
+ * mesh) a sample within fp32 rounding of an edge may be taken or rejected by either neighbour -- also by both: on-edge
+ * samples of a shared edge are not guaranteed watertight there; samples farther than rounding from every edge are.
+ * Also skipped: a face with a vertex index outside [0, V), a non-finite x / y, a NaN z, zero area, or an extent above
+ * ~1e34 pixels (its area overflows fp32).
  * workspace: gol_mesh_raster_workspace_bytes(B, F) bytes of device scratch (face records, packed tile bounds, the
  * per-view tile boxes and their in-box tile prefix).  The images are cleared by a streaming fill; only tiles inside a
  * view's mesh box are rasterized, by a fixed grid of workgroups that strides over them.
