@@ -1,7 +1,12 @@
-// gol_raster.h -- tile / wave / staging helpers shared by the tile rasterizers (raster.hip: 3 channels + extra,
-// raster_nd.hip: C channels).  Everything here is inline and file-local (anonymous namespace): each kernel file gets its
-// own copy, exactly as when it lived in raster.hip.
+// gol_raster.h -- what the tile rasterizers (raster.hip: 3 channels + extra, raster_nd.hip: C channels) have in common.
+// Tile / wave / staging helpers and the per-visit core that decides what is rendered: visit_falloff (sigma and
+// exp(-sigma), the only GOL_EXACT_MATH branch of that math), fwd_step / fwd_take, bwd_taken / bwd_recur / bwd_moments /
+// lane_sum, wave_last_entry, true_conic, and the host side of a launch (raster_grid,
+// GOL_RASTER_CHECK_DIMS, with_ppl).  Per kernel stay the LDS layouts, batch sizes, colour sums and the LAZY bookkeeping of
+// the fused forward.  Everything here is inline and file-local (anonymous namespace): each kernel file gets its own copy.
 #pragma once
+#include <type_traits>
+
 #include "gol_common.h"
 
 namespace {
@@ -10,8 +15,9 @@ constexpr int kBatch = 256;
 // conics are staged in LDS pre-multiplied by log2(e) -- alpha = opacity * 2^(-sigma') is one v_exp_f32 with a negated
 // operand instead of a multiply + exp per pixel -- and the diagonal terms by the 1/2 of sigma = (a dx^2 + c dy^2) / 2 +
 // b dx dy as well (GOL_SC_A / GOL_SC_B, applied where the records are written); kUnA / kUnB bring the true conic back
-// where the backward needs it
+// where the cull test and the backward's merges need it
 constexpr float kUnA = GOL_UN_A, kUnB = GOL_UN_B;
+__device__ __forceinline__ float3 true_conic(float a, float b, float c) { return make_float3(a * kUnA, b * kUnB, c * kUnA); }
 #ifdef GOL_EXACT_MATH
 // TEST-ONLY exact-math twin (goliath_amd/build.py, variant "exact"): the conic is staged unscaled, sigma is evaluated in
 // the order the CPU oracle (and gsplat) writes it -- 0.5 (a dx^2 + c dy^2) + b dx dy, every product and sum rounded
@@ -120,7 +126,8 @@ __device__ __forceinline__ Staged stage_entry(const float* __restrict__ records,
   s.a = q0;                              // x, y, a', b'
   s.b = q1;                              // c', opacity, r, g
   s.c = make_float2(q2.x, q2.y);         // b, extra
-  s.mask = wave_mask<PPL>(q0.x, q0.y, q0.z * kUnA, q0.w * kUnB, q1.x * kUnA, q2.z, q2.w, q3.x, q3.y, tile_x0, tile_y0);
+  const float3 cn = true_conic(q0.z, q0.w, q1.x);
+  s.mask = wave_mask<PPL>(q0.x, q0.y, cn.x, cn.y, cn.z, q2.z, q2.w, q3.x, q3.y, tile_x0, tile_y0);
   return s;
 }
 
@@ -131,5 +138,167 @@ __device__ __forceinline__ bool any_live(const V& live) {
   for (int q = 0; q < P; ++q) u |= __float_as_uint(live[q]);
   return u != 0u;
 }
+
+// ---- the per-visit core: one wave looks at one staged list entry ---------------------------------------------------------
+template <int PPL> using fvec = typename Pix<PPL>::fv;
+template <int PPL> using ivec = typename Pix<PPL>::iv;
+
+// sigma of the (staged) conic at the lane's pixels and e = exp(-gsplat's sigma); alpha = opacity * e
+template <int PPL>
+__device__ __forceinline__ void visit_falloff(float ca, float cb, float cc, float dx, const fvec<PPL>& dy, fvec<PPL>& sigma,
+                                              fvec<PPL>& e) {
+#ifndef GOL_EXACT_MATH
+  sigma = (ca * dx * dx + cc * dy * dy) + (cb * dx) * dy;  // log2e * gsplat's sigma
+#pragma unroll
+  for (int q = 0; q < PPL; ++q) e[q] = __builtin_amdgcn_exp2f(-sigma[q]);
+#else
+#pragma unroll
+  for (int q = 0; q < PPL; ++q) { sigma[q] = exact_sigma(ca, cb, cc, dx, dy[q]); e[q] = exact_exp_neg(sigma[q]); }
+#endif
+}
+
+// Forward: what the entry does to each pixel.  alpha = min(cap, opacity * e); live = 1 while the pixel composites.
+// Yields vis = alpha T (unmasked), next_T = T (1 - alpha), take[] and the lane masks of the pixels that stop here;
+// returns the union of those masks.
+template <int PPL>
+__device__ __forceinline__ unsigned long long fwd_step(const fvec<PPL>& sigma, fvec<PPL> alpha, const fvec<PPL>& live,
+                                                       const fvec<PPL>& T_cur, fvec<PPL>& vis, fvec<PPL>& next_T,
+                                                       bool (&take)[PPL], unsigned long long (&stop)[PPL]) {
+  alpha *= live;
+  vis = alpha * T_cur;
+#ifndef GOL_EXACT_MATH
+  next_T = T_cur - vis;  // = T (1 - alpha)
+#else
+#pragma unroll
+  for (int q = 0; q < PPL; ++q) next_T[q] = exact_next_T(T_cur[q], alpha[q]);
+#endif
+  // contributes: !(sigma < 0 || alpha < 1/255); stops: T (1 - alpha) <= 1e-4 (the stopping entry is not taken); one
+  // compare per pixel -- all as scalar lane masks (ballots of the plain compares; written with bools the compiler issues
+  // a second, NaN-aware compare for the negation).  (An early-out for visits without a taker, as the backward has it,
+  // does not pay here: 602-612 vs 613 us)
+  unsigned long long any_stop = 0ull;
+#pragma unroll
+  for (int q = 0; q < PPL; ++q) {
+    const unsigned long long mc = gol_ballot(!(sigma[q] < 0.f)) & gol_ballot(!(alpha[q] < GOL_ALPHA_FLOOR));
+    const unsigned long long ms = gol_ballot(next_T[q] <= GOL_T_STOP);
+    take[q] = __builtin_amdgcn_inverse_ballot_w64(mc & ~ms);
+    stop[q] = mc & ms;
+    any_stop |= stop[q];
+  }
+  return any_stop;
+}
+
+// Forward: vis becomes the taken pixels' weight (0 elsewhere) and T advances where the entry is taken
+template <int PPL>
+__device__ __forceinline__ void fwd_take(const bool (&take)[PPL], const fvec<PPL>& next_T, fvec<PPL>& vis, fvec<PPL>& T_cur) {
+#pragma unroll
+  for (int q = 0; q < PPL; ++q) vis[q] = take[q] ? vis[q] : 0.f;
+#ifndef GOL_EXACT_MATH
+  T_cur -= vis;                   // unchanged where the entry is not taken
+#else
+#pragma unroll
+  for (int q = 0; q < PPL; ++q) T_cur[q] = take[q] ? next_T[q] : T_cur[q];
+#endif
+}
+
+// Backward: capped alpha and the lane masks mv[] of the pixels that took entry li (within the pixel's list && !(sigma < 0
+// || alpha < 1/255): ballots of the plain compares, the ballot of a combined bool costs a v_cndmask + v_cmp); returns their union
+template <int PPL>
+__device__ __forceinline__ unsigned long long bwd_taken(float opacity, const fvec<PPL>& e, const fvec<PPL>& sigma, int li,
+                                                        const ivec<PPL>& bin_final, fvec<PPL>& alpha,
+                                                        unsigned long long (&mv)[PPL]) {
+  alpha = opacity * e;
+  unsigned long long many = 0ull;
+#pragma unroll
+  for (int q = 0; q < PPL; ++q) {
+    alpha[q] = fminf(GOL_ALPHA_CAP_BWD, alpha[q]);
+    mv[q] = gol_ballot(li <= bin_final[q]) & gol_ballot(!(sigma[q] < 0.f)) & gol_ballot(!(alpha[q] < GOL_ALPHA_FLOOR));
+    many |= mv[q];
+  }
+  return many;
+}
+
+// Backward: T steps back over the entry (T_cur becomes the transmittance in front of it); ra = 1 / (1 - alpha),
+// fac = alpha T = the entry's compositing weight
+template <int PPL>
+__device__ __forceinline__ void bwd_recur(const unsigned long long (&mv)[PPL], fvec<PPL>& alpha, fvec<PPL>& T_cur,
+                                          bool (&v)[PPL], fvec<PPL>& ra, fvec<PPL>& fac) {
+#pragma unroll
+  for (int q = 0; q < PPL; ++q) {
+    v[q] = __builtin_amdgcn_inverse_ballot_w64(mv[q]);
+    // an entry the pixel did not take enters with alpha = 0: 1 / (1 - 0) = 1 exactly, so T and the running sums pass
+    // through unchanged without further selects
+    alpha[q] = v[q] ? alpha[q] : 0.f;
+  }
+  const fvec<PPL> one_m = 1.f - alpha;
+#pragma unroll
+  for (int q = 0; q < PPL; ++q) ra[q] = __builtin_amdgcn_rcpf(one_m[q]);
+  const fvec<PPL> T_new = T_cur * ra;
+  fac = alpha * T_new;
+  T_cur = T_new;
+}
+
+// Backward: v_alpha and gop = e v_alpha with its first two moments in dy, per pixel (lane_sum adds a lane's pixels up).
+// gsplat: v_alpha = sum_c (rgb_c T - buffer_c ra) v_out_c + T_final ra (v_out_alpha - <bg, v_out>) with buffer_c = sum over
+// the Gaussians behind of rgb_c alpha T.  All channels enter through ONE dot product with the upstream gradient, w =
+// <colour, v_out>, so the colour buffers collapse into the running scalar q = sum_behind fac w: v_alpha = T w + ra (tail - q).
+// d loss / d sigma per pixel is -opacity * gop; the (wave-uniform) factor -opacity is applied once per Gaussian in
+// the merge step: the lanes reduce the moments of gop itself, whose zeroth moment IS v_opacity
+template <int PPL>
+__device__ __forceinline__ void bwd_moments(const fvec<PPL>& e, const fvec<PPL>& w, const fvec<PPL>& T_cur,
+                                            const fvec<PPL>& ra, const fvec<PPL>& fac, const fvec<PPL>& tail,
+                                            const bool (&v)[PPL], const fvec<PPL>& dy, fvec<PPL>& qsum, fvec<PPL>& gop,
+                                            fvec<PPL>& gy, fvec<PPL>& gyy) {
+  const fvec<PPL> v_alpha = T_cur * w + ra * (tail - qsum);
+  qsum += fac * w;
+  gop = e * v_alpha;
+#pragma unroll
+  for (int q = 0; q < PPL; ++q) gop[q] = v[q] ? gop[q] : 0.f;
+  gy = gop * dy;
+  gyy = gy * dy;
+}
+template <int PPL>
+__device__ __forceinline__ float lane_sum(const fvec<PPL>& x) {
+  float s = x[0];
+#pragma unroll
+  for (int q = 1; q < PPL; ++q) s += x[q];
+  return s;
+}
+
+// Backward start bound of a wave: the last list entry that any of its pixels took (wave-uniform)
+template <int PPL>
+__device__ __forceinline__ int wave_last_entry(const ivec<PPL>& bin_final) {
+  int wmax = bin_final[0];
+#pragma unroll
+  for (int q = 1; q < PPL; ++q) wmax = max(wmax, bin_final[q]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) wmax = max(wmax, __shfl_xor(wmax, off, 64));
+  return __builtin_amdgcn_readfirstlane(wmax);
+}
+
+// ---- host side of a launch -----------------------------------------------------------------------------------------------
+// grid.x of every raster launch: one workgroup per tile slot per view, tile rows padded to a multiple of 8 (tile_of_block)
+inline int64_t raster_grid(int B, int img_h, int img_w) {
+  return (int64_t)B * 8 * (((img_h + 15) / 16 + 7) / 8) * ((img_w + 15) / 16);
+}
+
+// size checks of the four raster entries (a macro: GOL_REQUIRE names the entry it fails in); the kernels address a view's
+// images with 32-bit byte offsets, bytes_per_pixel for the widest of them (0: the kernel has no such offsets)
+#define GOL_RASTER_CHECK_DIMS(bytes_per_pixel, too_large_msg)                                                           \
+  do {                                                                                                                  \
+    GOL_REQUIRE(B >= 0 && N >= 0, "negative size");                                                                     \
+    GOL_REQUIRE(block == 16, "only block_width == 16 is implemented (the reference's value, render_gsplat.py:28)");     \
+    GOL_REQUIRE(img_h > 0 && img_w > 0, "empty image");                                                                 \
+    GOL_REQUIRE(raster_grid(B, img_h, img_w) < (1ll << 31), "too many tiles");                                          \
+    GOL_REQUIRE((uint64_t)img_h * (uint64_t)img_w * (uint64_t)(bytes_per_pixel) < (1ull << 32), too_large_msg);         \
+  } while (0)
+
+// fn(std::integral_constant<int, ppl>) for ppl = 1 | 2: a launch spells its argument list once
+template <typename F>
+inline void with_ppl(int ppl, F&& fn) {
+  if (ppl == 2) fn(std::integral_constant<int, 2>());
+  else fn(std::integral_constant<int, 1>());
+}
+constexpr std::true_type kYes{}; constexpr std::false_type kNo{};   // compile-time switches of a launch lambda
 
 }  // namespace

@@ -117,59 +117,26 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_fwd_kernel(
         // branch-free pixel update: selects instead of exec-mask regions (the loop is issue-bound)
         const float dx = a4.x - px;
         const fv dy = a4.y - py;
-        fv sigma, alpha;
-#ifndef GOL_EXACT_MATH
-        sigma = (a4.z * dx * dx + b4.x * dy * dy) + (a4.w * dx) * dy;  // log2e * gsplat's sigma
+        fv sigma, e, alpha, vis, next_T;
+        visit_falloff<PPL>(a4.z, a4.w, b4.x, dx, dy, sigma, e);
 #pragma unroll
-        for (int q = 0; q < PPL; ++q) alpha[q] = fminf(GOL_ALPHA_CAP_FWD, b4.y * __builtin_amdgcn_exp2f(-sigma[q]));
-#else
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) {
-          sigma[q] = exact_sigma(a4.z, a4.w, b4.x, dx, dy[q]);
-          alpha[q] = fminf(GOL_ALPHA_CAP_FWD, b4.y * exact_exp_neg(sigma[q]));
-        }
-#endif
-        alpha *= live;
-        fv vis = alpha * T_cur;
-#ifndef GOL_EXACT_MATH
-        const fv next_T = T_cur - vis;  // = T (1 - alpha)
-#else
-        fv next_T;
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) next_T[q] = exact_next_T(T_cur[q], alpha[q]);
-#endif
-        // contributes: !(sigma < 0 || alpha < 1/255); stop / take: one compare per pixel -- all as scalar lane masks
-        // (ballots of the plain compares; written with bools the compiler issues a second, NaN-aware compare for the
-        // negation).  (An early-out for visits without a taker, as the backward has it, does not pay here: 602-612 vs 613 us)
-        unsigned long long mc[PPL], ms[PPL], any_stop = 0ull;
+        for (int q = 0; q < PPL; ++q) alpha[q] = fminf(GOL_ALPHA_CAP_FWD, b4.y * e[q]);
         bool take[PPL];
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) {
-          mc[q] = gol_ballot(!(sigma[q] < 0.f)) & gol_ballot(!(alpha[q] < GOL_ALPHA_FLOOR));
-          ms[q] = gol_ballot(next_T[q] <= GOL_T_STOP);
-          take[q] = __builtin_amdgcn_inverse_ballot_w64(mc[q] & ~ms[q]);
-          any_stop |= mc[q] & ms[q];
-        }
+        unsigned long long stop_m[PPL];
+        const unsigned long long any_stop = fwd_step<PPL>(sigma, alpha, live, T_cur, vis, next_T, take, stop_m);
         bool half_done = false;
         if (!LAZY || any_stop != 0ull) {   // LAZY: wave-uniform and rare -- some pixel stops here
 #pragma unroll
           for (int q = 0; q < PPL; ++q) {
-            const bool stop = __builtin_amdgcn_inverse_ballot_w64(mc[q] & ms[q]);
+            const bool stop = __builtin_amdgcn_inverse_ballot_w64(stop_m[q]);
             live[q] = stop ? 0.f : live[q];
             if (LAZY) cur_idx[q] = stop ? (batch_start + t - 1) : cur_idx[q];
           }
           if (LAZY) half_done = gol_ballot(any_live<fv, PPL>(live)) == 0ull;
         }
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) vis[q] = take[q] ? vis[q] : 0.f;
+        fwd_take<PPL>(take, next_T, vis, T_cur);
         acc0 += b4.z * vis; acc1 += b4.w * vis; acc2 += c2.x * vis;
         if (EXTRA) acc3 += c2.y * vis;
-#ifndef GOL_EXACT_MATH
-        T_cur -= vis;                   // unchanged where the entry is not taken
-#else
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) T_cur[q] = take[q] ? next_T[q] : T_cur[q];
-#endif
         if (!LAZY) {
 #pragma unroll
           for (int q = 0; q < PPL; ++q) cur_idx[q] = take[q] ? (batch_start + t) : cur_idx[q];
@@ -373,12 +340,7 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
   const fv tail = T_final * (voa - (background[0] * vo0 + background[1] * vo1 + background[2] * vo2));
   fv qsum = 0.f;  // running sum over the Gaussians behind of fac * <colour, v_out>
 
-  int wmax = bin_final[0];
-#pragma unroll
-  for (int q = 1; q < PPL; ++q) wmax = max(wmax, bin_final[q]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) wmax = max(wmax, __shfl_xor(wmax, off, 64));
-  wmax = __builtin_amdgcn_readfirstlane(wmax);
+  const int wmax = wave_last_entry<PPL>(bin_final);
   if (lane == 0) s_wmax[wave] = wmax;
   __syncthreads();
   int bmax = s_wmax[0];
@@ -427,72 +389,30 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
       const int li = batch_end - t;
       const float dx = a4.x - px;
       const fv dy = a4.y - py;
-      fv sigma, vis;
-#ifndef GOL_EXACT_MATH
-      sigma = (a4.z * dx * dx + b4.x * dy * dy) + (a4.w * dx) * dy;
-#pragma unroll
-      for (int q = 0; q < PPL; ++q) vis[q] = __builtin_amdgcn_exp2f(-sigma[q]);  // sigma = log2e * gsplat's
-#else
-#pragma unroll
-      for (int q = 0; q < PPL; ++q) { sigma[q] = exact_sigma(a4.z, a4.w, b4.x, dx, dy[q]); vis[q] = exact_exp_neg(sigma[q]); }
-#endif
-      fv alpha = b4.y * vis;
-      // taken by the pixel: within its list && !(sigma < 0 || alpha < 1/255) -- as scalar lane masks (ballots of the plain
-      // compares; the ballot of a combined bool costs a v_cndmask + v_cmp)
-      unsigned long long mv[PPL], many = 0ull;
-#pragma unroll
-      for (int q = 0; q < PPL; ++q) {
-        alpha[q] = fminf(GOL_ALPHA_CAP_BWD, alpha[q]);
-        mv[q] = gol_ballot(li <= bin_final[q]) & gol_ballot(!(sigma[q] < 0.f)) & gol_ballot(!(alpha[q] < GOL_ALPHA_FLOOR));
-        many |= mv[q];
-      }
-      if (many == 0ull) continue;
+      fv sigma, vis, alpha, ra, fac;
+      visit_falloff<PPL>(a4.z, a4.w, b4.x, dx, dy, sigma, vis);
+      unsigned long long mv[PPL];
+      if (bwd_taken<PPL>(b4.y, vis, sigma, li, bin_final, alpha, mv) == 0ull) continue;
       bool v[PPL];
-      fv ra;
-#pragma unroll
-      for (int q = 0; q < PPL; ++q) {
-        v[q] = __builtin_amdgcn_inverse_ballot_w64(mv[q]);
-        // an entry the pixel did not take enters with alpha = 0: 1 / (1 - 0) = 1 exactly, so T and the running sums pass
-        // through unchanged without further selects
-        alpha[q] = v[q] ? alpha[q] : 0.f;
-      }
-      const fv one_m = 1.f - alpha;
-#pragma unroll
-      for (int q = 0; q < PPL; ++q) ra[q] = __builtin_amdgcn_rcpf(one_m[q]);
-      const fv T_new = T_cur * ra;
-      const fv fac = alpha * T_new;
-      T_cur = T_new;
-      // gsplat: v_alpha = sum_c (rgb_c T - buffer_c ra) v_out_c + T_final ra (v_out_alpha - <bg, v_out>) with
-      // buffer_c = sum over the Gaussians behind of rgb_c alpha T.  All channels enter through ONE dot product with the
-      // upstream gradient, w = <colour, v_out>, so the three running colour buffers collapse into the running scalar
-      // q = sum_behind fac w:  v_alpha = T w + ra (tail - q)
+      bwd_recur<PPL>(mv, alpha, T_cur, v, ra, fac);
+      // all channels enter through ONE dot product with the upstream gradient (see bwd_moments)
       fv w = b4.z * vo0 + b4.w * vo1 + c2.x * vo2;
       if (EXTRA) w += c2.y * vo3;
-      const fv v_alpha = T_new * w + ra * (tail - qsum);
-      qsum += fac * w;
-      // d loss / d sigma per pixel is -opacity * gop; the (wave-uniform) factor -opacity is applied once per Gaussian in
-      // the merge step: the lanes reduce the moments of gop itself, whose zeroth moment IS v_opacity
-      fv gop = vis * v_alpha;
-#pragma unroll
-      for (int q = 0; q < PPL; ++q) gop[q] = v[q] ? gop[q] : 0.f;
-      const fv gy = gop * dy;
-      const fv gyy = gy * dy;
-      // the lane's pixels, summed (PPL = 2: one multiply + one scalar FMA per colour sum -- written on scalars: from the
-      // 2-vector form the compiler builds v_mul + v_pk_fma and throws the packed op's upper half away)
-      float g0s, g1s, g2s, g3 = 0.f, m0, my, myy;
+      fv gop, gy, gyy;
+      bwd_moments<PPL>(vis, w, T_cur, ra, fac, tail, v, dy, qsum, gop, gy, gyy);
+      // the colour sums of the lane's pixels (PPL = 2: one multiply + one scalar FMA per colour sum -- written on scalars:
+      // from the 2-vector form the compiler builds v_mul + v_pk_fma and throws the packed op's upper half away)
+      float g0s, g1s, g2s, g3 = 0.f;
       if (PPL == 2) {
         g0s = __builtin_fmaf(fac[0], vo0[0], fac[PPL - 1] * vo0[PPL - 1]);
         g1s = __builtin_fmaf(fac[0], vo1[0], fac[PPL - 1] * vo1[PPL - 1]);
         g2s = __builtin_fmaf(fac[0], vo2[0], fac[PPL - 1] * vo2[PPL - 1]);
         if (EXTRA) g3 = __builtin_fmaf(fac[0], vo3[0], fac[PPL - 1] * vo3[PPL - 1]);
-        m0 = gop[0] + gop[PPL - 1];       // sum_pix gop
-        my = gy[0] + gy[PPL - 1];         // sum gop dy
-        myy = gyy[0] + gyy[PPL - 1];
       } else {
         g0s = fac[0] * vo0[0]; g1s = fac[0] * vo1[0]; g2s = fac[0] * vo2[0];
         if (EXTRA) g3 = fac[0] * vo3[0];
-        m0 = gop[0]; my = gy[0]; myy = gyy[0];
       }
+      const float m0 = lane_sum<PPL>(gop), my = lane_sum<PPL>(gy), myy = lane_sum<PPL>(gyy);
       const float mx = m0 * dx, mxx = mx * dx, mxy = my * dx;
       const float r0 = gol_wave_sum4(g0s, g1s, g2s, m0);
       const float r1 = gol_wave_sum4(mx, my, mxx, mxy);
@@ -518,6 +438,7 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
 #pragma unroll
         for (int w = 0; w < NW; ++w) any = any || (s_touched[w][t] != 0);
         if (!any || c > (EXTRA ? 9 : 8)) continue;
+        // (the three merges keep their own arithmetic form of the weights: a common one changes these kernels' code)
         // component c = w1 * S[k1] + w2 * S[k2] of the wave-summed slots S; slots 4..8 hold moments of gop:
         // v_sigma-sums = -opacity * moment (conic back from its log2e scaling with ln 2)
         const float4 a4 = s_e[t].a;
@@ -557,11 +478,12 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
         const float4 a4 = s_e[tid].a;
         const float4 b4 = s_e[tid].b;
         const float nop = -b4.y;  // slots 4..8 are moments of gop: v_sigma-sums = -opacity * moment
-        const float ca = a4.z * kUnA, cb = a4.w * kUnB, cc = b4.x * kUnA;
+        // (the packed merge's weights with -opacity factored out of the x / y sums: one thread forms all of them)
+        const float3 cn = true_conic(a4.z, a4.w, b4.x);
         atomicAdd(v_colors + 3 * g, a[0]); atomicAdd(v_colors + 3 * g + 1, a[1]); atomicAdd(v_colors + 3 * g + 2, a[2]);
         atomicAdd(v_opacity + g, a[3]);
-        atomicAdd(v_xy + 2 * g, nop * (ca * a[4] + cb * a[5]));
-        atomicAdd(v_xy + 2 * g + 1, nop * (cb * a[4] + cc * a[5]));
+        atomicAdd(v_xy + 2 * g, nop * (cn.x * a[4] + cn.y * a[5]));
+        atomicAdd(v_xy + 2 * g + 1, nop * (cn.y * a[4] + cn.z * a[5]));
         atomicAdd(v_conic + 3 * g, 0.5f * nop * a[6]); atomicAdd(v_conic + 3 * g + 1, nop * a[7]);
         atomicAdd(v_conic + 3 * g + 2, 0.5f * nop * a[8]);
         if (EXTRA && v_extra) atomicAdd(v_extra + g, a[9]);
@@ -594,14 +516,11 @@ __global__ __launch_bounds__(256) void raster_count_pairs_kernel(int N, int img_
       const float4* R = reinterpret_cast<const float4*>(records + ((size_t)view * N + sorted_ids[(size_t)view * capacity + li]) * GOL_SPLAT_RECORD);
       const float4 q0 = R[0], q1 = R[1];
       const float dx = q0.x - px, dy = q0.y - py;
-      const float sg = (q0.z * dx * dx + q1.x * dy * dy) + (q0.w * dx) * dy;
-#ifndef GOL_EXACT_MATH
-      const float alpha = fminf(GOL_ALPHA_CAP_FWD, q1.y * __builtin_amdgcn_exp2f(-sg));
-#else
-      const float alpha = fminf(GOL_ALPHA_CAP_FWD, q1.y * expf(-sg));
-#endif
+      f1 sg, e;
+      visit_falloff<1>(q0.z, q0.w, q1.x, dx, f1(dy), sg, e);
+      const float alpha = fminf(GOL_ALPHA_CAP_FWD, q1.y * e[0]);
       ++tested;
-      taken += (!(sg < 0.f) && !(alpha < GOL_ALPHA_FLOOR)) ? 1 : 0;
+      taken += (!(sg[0] < 0.f) && !(alpha < GOL_ALPHA_FLOOR)) ? 1 : 0;
     }
   }
   atomicAdd(&s_cnt[0], tested);
@@ -678,13 +597,9 @@ extern "C" int gol_rasterize_fwd(int B, int N, int img_h, int img_w, int block, 
                                  float* out_extra_norm, float norm_lo, const float* l1_target, const float* l1_mask,
                                  int l1_mask_c, uint8_t* l1_sign, float* l1_partial, float* l1_out, float l1_scale,
                                  int pixels_per_lane, void* stream) {
-  GOL_REQUIRE(B >= 0 && N >= 0, "negative size");
-  GOL_REQUIRE(block == 16, "only block_width == 16 is implemented (the reference's value, render_gsplat.py:28)");
-  GOL_REQUIRE(img_h > 0 && img_w > 0, "empty image");
+  GOL_RASTER_CHECK_DIMS(12, "image too large (32-bit byte offsets inside a view)");
   if (B == 0) return GOL_OK;
-  GOL_REQUIRE((int64_t)B * 8 * (((img_h + 15) / 16 + 7) / 8) * ((img_w + 15) / 16) < (1ll << 31), "too many tiles");
   GOL_REQUIRE(tile_bins && background && out_img && final_Ts && final_idx, "null pointer");
-  GOL_REQUIRE((uint64_t)img_h * (uint64_t)img_w * 12ull < (1ull << 32), "image too large (32-bit byte offsets inside a view)");
   GOL_REQUIRE(capacity == 0 || sorted_ids, "null sorted_ids");
   GOL_REQUIRE(N == 0 || records, "null Gaussian records");
   GOL_REQUIRE((!out_extra && !out_extra_norm) || with_extra || N == 0, "out_extra / out_extra_norm need the extra channel");
@@ -693,7 +608,7 @@ extern "C" int gol_rasterize_fwd(int B, int N, int img_h, int img_w, int block, 
   GOL_REQUIRE(!l1_mask || (l1_target && (l1_mask_c == 1 || l1_mask_c == 3)), "l1_mask: 1 or 3 channels, with l1_target");
   GOL_REQUIRE(!l1_out || l1_target, "l1_out needs l1_target");
   const int tiles_x = (img_w + 15) / 16, tiles_y = (img_h + 15) / 16;
-  dim3 grid(8 * ((tiles_y + 7) / 8) * tiles_x * B);
+  const dim3 grid((unsigned)raster_grid(B, img_h, img_w));
   const int2* bins = reinterpret_cast<const int2*>(tile_bins);
   hipStream_t s = (hipStream_t)stream;
   GOL_REQUIRE(pixels_per_lane >= 0 && pixels_per_lane <= 2, "pixels_per_lane: 0 (choose by B), 1 or 2");
@@ -701,26 +616,22 @@ extern "C" int gol_rasterize_fwd(int B, int N, int img_h, int img_w, int block, 
   // through one wave, which the finer footprint shortens to ~0.55x for ~9 % more instructions in total (see Pix)
   int ppl = pixels_per_lane;
   if (ppl == 0) gol_raster_plan(B, &ppl);
-#define GOL_LAUNCH_FWD(EX, LZ)                                                                                          \
-  do {                                                                                                                  \
-    if (ppl == 2)                                                                                                       \
-      raster_fwd_kernel<EX, LZ, 2><<<grid, 128, 0, s>>>(N, img_h, img_w, planar, tiles_x, tiles_y, bins, sorted_ids,   \
-                                                        capacity, records, background, out_img, out_extra, final_Ts,   \
-                                                        final_idx, out_alpha, EX ? out_extra_norm : nullptr, norm_lo,   \
-                                                        l1_target, l1_mask, l1_mask_c, l1_sign, l1_partial, B);         \
-    else                                                                                                                \
-      raster_fwd_kernel<EX, LZ, 1><<<grid, 256, 0, s>>>(N, img_h, img_w, planar, tiles_x, tiles_y, bins, sorted_ids,   \
-                                                        capacity, records, background, out_img, out_extra, final_Ts,   \
-                                                        final_idx, out_alpha, EX ? out_extra_norm : nullptr, norm_lo,   \
-                                                        l1_target, l1_mask, l1_mask_c, l1_sign, l1_partial, B);         \
-  } while (0)
+  auto launch = [&](auto ex_c, auto lazy_c) {
+    with_ppl(ppl, [&](auto ppl_c) {
+      constexpr bool EX = decltype(ex_c)::value, LZ = decltype(lazy_c)::value;
+      constexpr int PPL = decltype(ppl_c)::value;
+      raster_fwd_kernel<EX, LZ, PPL><<<grid, 64 * Pix<PPL>::kWaves, 0, s>>>(
+          N, img_h, img_w, planar, tiles_x, tiles_y, bins, sorted_ids, capacity, records, background, out_img, out_extra,
+          final_Ts, final_idx, out_alpha, EX ? out_extra_norm : nullptr, norm_lo, l1_target, l1_mask, l1_mask_c, l1_sign,
+          l1_partial, B);
+    });
+  };
   const bool ex = out_extra || out_extra_norm;
   // planar = the fused path: final_idx is the backward's start bound (see raster_fwd_kernel); gsplat's layout: exact
-  if (ex && planar) GOL_LAUNCH_FWD(true, true);
-  else if (ex) GOL_LAUNCH_FWD(true, false);
-  else if (planar) GOL_LAUNCH_FWD(false, true);
-  else GOL_LAUNCH_FWD(false, false);
-#undef GOL_LAUNCH_FWD
+  if (ex && planar) launch(kYes, kYes);
+  else if (ex) launch(kYes, kNo);
+  else if (planar) launch(kNo, kYes);
+  else launch(kNo, kNo);
   if (l1_out) l1_sum_kernel<<<1, 1024, 0, s>>>(B * tiles_x * tiles_y, l1_partial, l1_scale, l1_out);
   GOL_CHECK_LAUNCH();
   return GOL_OK;
@@ -734,11 +645,8 @@ extern "C" int gol_rasterize_bwd(int B, int N, int img_h, int img_w, int block, 
                                  float* v_extra, float* v_opacity, int grad_stride, const uint8_t* v_sign,
                                  const float* v_sign_mask, int v_sign_mask_c, const float* v_img_scale,
                                  float v_img_scale_mul, int pixels_per_lane, void* stream) {
-  GOL_REQUIRE(B >= 0 && N >= 0, "negative size");
-  GOL_REQUIRE(block == 16, "only block_width == 16 is implemented (the reference's value, render_gsplat.py:28)");
-  GOL_REQUIRE(img_h > 0 && img_w > 0, "empty image");
+  GOL_RASTER_CHECK_DIMS(0, "");   // 0: no 32-bit image offsets in this kernel, no image-size bound
   if (B == 0 || N == 0 || capacity == 0) return GOL_OK;
-  GOL_REQUIRE((int64_t)B * 8 * (((img_h + 15) / 16 + 7) / 8) * ((img_w + 15) / 16) < (1ll << 31), "too many tiles");
   GOL_REQUIRE(tile_bins && sorted_ids && background && final_Ts && final_idx, "null pointer");
   GOL_REQUIRE(v_out_img || v_sign, "no upstream image gradient (v_out_img or v_sign)");
   GOL_REQUIRE(!v_sign || planar, "the sign image of the fused L1 goes with planar images");
@@ -753,32 +661,26 @@ extern "C" int gol_rasterize_bwd(int B, int N, int img_h, int img_w, int block, 
                     (!v_extra || v_extra == v_colors + 9),
                 "record layout is [rgb | opacity | xy | conic | extra | pad] (GOL_GRAD_RECORD floats)");
   const int tiles_x = (img_w + 15) / 16, tiles_y = (img_h + 15) / 16;
-  dim3 grid(8 * ((tiles_y + 7) / 8) * tiles_x * B);
+  const dim3 grid((unsigned)raster_grid(B, img_h, img_w));
   const int2* bins = reinterpret_cast<const int2*>(tile_bins);
   hipStream_t s = (hipStream_t)stream;
   GOL_REQUIRE(pixels_per_lane >= 0 && pixels_per_lane <= 2, "pixels_per_lane: 0 (2), 1 or 2");
   const int ppl = pixels_per_lane ? pixels_per_lane : 2;
   const bool ex = with_extra && (v_out_extra || v_extra);
-#define GOL_LAUNCH_BWD(EX, PK)                                                                                          \
-  do {                                                                                                                  \
-    if (ppl == 2)                                                                                                       \
-      raster_bwd_kernel<EX, PK, 2><<<grid, 128, 0, s>>>(N, img_h, img_w, planar, tiles_x, tiles_y, bins, sorted_ids,   \
-                                                        capacity, records, background, final_Ts, final_idx, v_out_img, \
-                                                        EX ? v_out_extra : nullptr, v_out_alpha, v_xy, v_conic,        \
-                                                        v_colors, EX ? v_extra : nullptr, v_opacity, v_sign,           \
-                                                        v_sign_mask, v_sign_mask_c, v_img_scale, v_img_scale_mul, B);  \
-    else                                                                                                                \
-      raster_bwd_kernel<EX, PK, 1><<<grid, 256, 0, s>>>(N, img_h, img_w, planar, tiles_x, tiles_y, bins, sorted_ids,   \
-                                                        capacity, records, background, final_Ts, final_idx, v_out_img, \
-                                                        EX ? v_out_extra : nullptr, v_out_alpha, v_xy, v_conic,        \
-                                                        v_colors, EX ? v_extra : nullptr, v_opacity, v_sign,           \
-                                                        v_sign_mask, v_sign_mask_c, v_img_scale, v_img_scale_mul, B);  \
-  } while (0)
-  if (ex && packed) GOL_LAUNCH_BWD(true, true);
-  else if (ex) GOL_LAUNCH_BWD(true, false);
-  else if (packed) GOL_LAUNCH_BWD(false, true);
-  else GOL_LAUNCH_BWD(false, false);
-#undef GOL_LAUNCH_BWD
+  auto launch = [&](auto ex_c, auto packed_c) {
+    with_ppl(ppl, [&](auto ppl_c) {
+      constexpr bool EX = decltype(ex_c)::value, PK = decltype(packed_c)::value;
+      constexpr int PPL = decltype(ppl_c)::value;
+      raster_bwd_kernel<EX, PK, PPL><<<grid, 64 * Pix<PPL>::kWaves, 0, s>>>(
+          N, img_h, img_w, planar, tiles_x, tiles_y, bins, sorted_ids, capacity, records, background, final_Ts, final_idx,
+          v_out_img, EX ? v_out_extra : nullptr, v_out_alpha, v_xy, v_conic, v_colors, EX ? v_extra : nullptr, v_opacity,
+          v_sign, v_sign_mask, v_sign_mask_c, v_img_scale, v_img_scale_mul, B);
+    });
+  };
+  if (ex && packed) launch(kYes, kYes);
+  else if (ex) launch(kYes, kNo);
+  else if (packed) launch(kNo, kYes);
+  else launch(kNo, kNo);
   GOL_CHECK_LAUNCH();
   return GOL_OK;
 }

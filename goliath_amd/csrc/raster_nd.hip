@@ -107,47 +107,19 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_fwd_kernel(
         const float2 b2 = s_b[t];
         const float dx = a4.x - px;
         const fv dy = a4.y - py;
-        fv sigma, alpha;
-#ifndef GOL_EXACT_MATH
-        sigma = (a4.z * dx * dx + b2.x * dy * dy) + (a4.w * dx) * dy;  // log2e * gsplat's sigma
+        fv sigma, e, alpha, vis, next_T;
+        visit_falloff<PPL>(a4.z, a4.w, b2.x, dx, dy, sigma, e);
 #pragma unroll
-        for (int q = 0; q < PPL; ++q) alpha[q] = fminf(GOL_ALPHA_CAP_FWD, b2.y * __builtin_amdgcn_exp2f(-sigma[q]));
-#else
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) {
-          sigma[q] = exact_sigma(a4.z, a4.w, b2.x, dx, dy[q]);
-          alpha[q] = fminf(GOL_ALPHA_CAP_FWD, b2.y * exact_exp_neg(sigma[q]));
-        }
-#endif
-        alpha *= live;
-        fv vis = alpha * T_cur;
-#ifndef GOL_EXACT_MATH
-        const fv next_T = T_cur - vis;  // = T (1 - alpha)
-#else
-        fv next_T;
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) next_T[q] = exact_next_T(T_cur[q], alpha[q]);
-#endif
-        // contributes: !(sigma < 0 || alpha < 1/255); stops: T (1 - alpha) <= 1e-4 (the stopping entry is not taken)
+        for (int q = 0; q < PPL; ++q) alpha[q] = fminf(GOL_ALPHA_CAP_FWD, b2.y * e[q]);
         bool take[PPL];
+        unsigned long long stop_m[PPL];
+        fwd_step<PPL>(sigma, alpha, live, T_cur, vis, next_T, take, stop_m);
 #pragma unroll
-        for (int q = 0; q < PPL; ++q) {
-          const unsigned long long mc = gol_ballot(!(sigma[q] < 0.f)) & gol_ballot(!(alpha[q] < GOL_ALPHA_FLOOR));
-          const unsigned long long ms = gol_ballot(next_T[q] <= GOL_T_STOP);
-          take[q] = __builtin_amdgcn_inverse_ballot_w64(mc & ~ms);
-          const bool stop = __builtin_amdgcn_inverse_ballot_w64(mc & ms);
-          live[q] = stop ? 0.f : live[q];
-          vis[q] = take[q] ? vis[q] : 0.f;
-        }
+        for (int q = 0; q < PPL; ++q) live[q] = __builtin_amdgcn_inverse_ballot_w64(stop_m[q]) ? 0.f : live[q];
+        fwd_take<PPL>(take, next_T, vis, T_cur);
         const float* col = s_col + t * CK;
 #pragma unroll
         for (int c = 0; c < CK; ++c) acc[c] += col[c] * vis;
-#ifndef GOL_EXACT_MATH
-        T_cur -= vis;                   // unchanged where the entry is not taken
-#else
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) T_cur[q] = take[q] ? next_T[q] : T_cur[q];
-#endif
 #pragma unroll
         for (int q = 0; q < PPL; ++q) cur_idx[q] = take[q] ? (batch_start + t) : cur_idx[q];
       }
@@ -236,12 +208,7 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
     }
   }
 
-  int wmax = bin_final[0];
-#pragma unroll
-  for (int q = 1; q < PPL; ++q) wmax = max(wmax, bin_final[q]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) wmax = max(wmax, __shfl_xor(wmax, off, 64));
-  wmax = __builtin_amdgcn_readfirstlane(wmax);
+  const int wmax = wave_last_entry<PPL>(bin_final);
   if (lane == 0) s_wmax[wave] = wmax;
   __syncthreads();
   int bmax = s_wmax[0];
@@ -290,49 +257,19 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
       const int li = batch_end - t;
       const float dx = a4.x - px;
       const fv dy = a4.y - py;
-      fv sigma, vis;
-#ifndef GOL_EXACT_MATH
-      sigma = (a4.z * dx * dx + b2.x * dy * dy) + (a4.w * dx) * dy;
-#pragma unroll
-      for (int q = 0; q < PPL; ++q) vis[q] = __builtin_amdgcn_exp2f(-sigma[q]);  // sigma = log2e * gsplat's
-#else
-#pragma unroll
-      for (int q = 0; q < PPL; ++q) { sigma[q] = exact_sigma(a4.z, a4.w, b2.x, dx, dy[q]); vis[q] = exact_exp_neg(sigma[q]); }
-#endif
-      fv alpha = b2.y * vis;
-      unsigned long long mv[PPL], many = 0ull;
-#pragma unroll
-      for (int q = 0; q < PPL; ++q) {
-        alpha[q] = fminf(GOL_ALPHA_CAP_BWD, alpha[q]);
-        mv[q] = gol_ballot(li <= bin_final[q]) & gol_ballot(!(sigma[q] < 0.f)) & gol_ballot(!(alpha[q] < GOL_ALPHA_FLOOR));
-        many |= mv[q];
-      }
-      if (many == 0ull) continue;
+      fv sigma, vis, alpha, ra, fac;
+      visit_falloff<PPL>(a4.z, a4.w, b2.x, dx, dy, sigma, vis);
+      unsigned long long mv[PPL];
+      if (bwd_taken<PPL>(b2.y, vis, sigma, li, bin_final, alpha, mv) == 0ull) continue;
       bool v[PPL];
-      fv ra;
-#pragma unroll
-      for (int q = 0; q < PPL; ++q) {
-        v[q] = __builtin_amdgcn_inverse_ballot_w64(mv[q]);
-        alpha[q] = v[q] ? alpha[q] : 0.f;   // not taken: alpha = 0 passes T and the running sums through unchanged
-      }
-      const fv one_m = 1.f - alpha;
-#pragma unroll
-      for (int q = 0; q < PPL; ++q) ra[q] = __builtin_amdgcn_rcpf(one_m[q]);
-      const fv T_new = T_cur * ra;
-      const fv fac = alpha * T_new;
-      T_cur = T_new;
-      // v_alpha = T w + ra (tail - q) with w = <colour, v_out> over this chunk's channels (see raster_bwd_kernel)
+      bwd_recur<PPL>(mv, alpha, T_cur, v, ra, fac);
+      // w = <colour, v_out> over this chunk's channels (see bwd_moments)
       const float* col = s_col + t * CK;
       fv w = 0.f;
 #pragma unroll
       for (int c = 0; c < CK; ++c) w += col[c] * vo[c];
-      const fv v_alpha = T_new * w + ra * (tail - qsum);
-      qsum += fac * w;
-      fv gop = vis * v_alpha;
-#pragma unroll
-      for (int q = 0; q < PPL; ++q) gop[q] = v[q] ? gop[q] : 0.f;
-      const fv gy = gop * dy;
-      const fv gyy = gy * dy;
+      fv gop, gy, gyy;
+      bwd_moments<PPL>(vis, w, T_cur, ra, fac, tail, v, dy, qsum, gop, gy, gyy);
       float s[kRow];
 #pragma unroll
       for (int c = 0; c < CK; ++c) {
@@ -340,9 +277,7 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
 #pragma unroll
         for (int q = 1; q < PPL; ++q) s[c] = __builtin_fmaf(fac[q], vo[c][q], s[c]);
       }
-      float m0 = gop[0], my = gy[0], myy = gyy[0];
-#pragma unroll
-      for (int q = 1; q < PPL; ++q) { m0 += gop[q]; my += gy[q]; myy += gyy[q]; }
+      const float m0 = lane_sum<PPL>(gop), my = lane_sum<PPL>(gy), myy = lane_sum<PPL>(gyy);
       const float mx = m0 * dx;
       s[CK + 0] = m0; s[CK + 1] = mx; s[CK + 2] = my; s[CK + 3] = mx * dx; s[CK + 4] = my * dx; s[CK + 5] = myy;
 #pragma unroll
@@ -371,7 +306,8 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
       const float4 a4 = s_a[t];
       const float2 b2 = s_b[t];
       const float nop = -b2.y;   // d loss / d sigma = -opacity * gop: moments of gop -> sigma sums
-      const float ca = a4.z * kUnA, cb = a4.w * kUnB, cc = b2.x * kUnA;
+      const float3 cn = true_conic(a4.z, a4.w, b2.x);
+      const float ca = cn.x, cb = cn.y, cc = cn.z;
       int k1 = k, k2 = k;
       float w1 = 1.f, w2 = 0.f;
       float* dst;
@@ -410,26 +346,31 @@ NdPlan nd_plan(int C) {
   return p;
 }
 
-}  // namespace
+// fn(std::integral_constant<int, CK>, chunks in grid.y, first channel) for every launch of nd_plan(C); false: no such CK
+template <typename F>
+bool for_nd_launches(int C, F&& fn) {
+  const NdPlan pl = nd_plan(C);
+  if (pl.n16 > 0) fn(std::integral_constant<int, 16>(), pl.n16, 0);
+  switch (pl.tail) {
+    case 0: break;
+    case 1: fn(std::integral_constant<int, 1>(), 1, pl.tail_first); break;
+    case 2: fn(std::integral_constant<int, 2>(), 1, pl.tail_first); break;
+    case 4: fn(std::integral_constant<int, 4>(), 1, pl.tail_first); break;
+    case 8: fn(std::integral_constant<int, 8>(), 1, pl.tail_first); break;
+    default: return false;
+  }
+  return true;
+}
 
-// argument checks shared by both entries (a macro: GOL_REQUIRE names the entry it fails in)
-#define GOL_ND_CHECK()                                                                                                  \
-  do {                                                                                                                  \
-    GOL_REQUIRE(B >= 0 && N >= 0, "negative size");                                                                     \
-    GOL_REQUIRE(C >= 1, "C >= 1 colour channels");                                                                      \
-    GOL_REQUIRE(C <= 16 * 65535, "too many colour channels (at most 1048560: one launch row of 16-channel chunks)");     \
-    GOL_REQUIRE(block == 16, "only block_width == 16 is implemented (the reference's value, render_gsplat.py:28)");     \
-    GOL_REQUIRE(img_h > 0 && img_w > 0, "empty image");                                                                 \
-    GOL_REQUIRE((int64_t)B * 8 * (((img_h + 15) / 16 + 7) / 8) * ((img_w + 15) / 16) < (1ll << 31), "too many tiles");  \
-    GOL_REQUIRE((uint64_t)img_h * (uint64_t)img_w * (uint64_t)C * 4ull < (1ull << 32),                                  \
-                "image too large (32-bit byte offsets inside a view: H * W * C * 4 bytes)");                            \
-  } while (0)
+}  // namespace
 
 extern "C" int gol_rasterize_nd_fwd(int B, int N, int C, int img_h, int img_w, int block, const int32_t* tile_bins,
                                     const int32_t* sorted_ids, int64_t capacity, const float* records, const float* colors,
                                     const float* background, float* out_img, float* final_Ts, int32_t* final_idx,
                                     int pixels_per_lane, void* stream) {
-  GOL_ND_CHECK();
+  GOL_REQUIRE(C >= 1, "C >= 1 colour channels");
+  GOL_REQUIRE(C <= 16 * 65535, "too many colour channels (at most 1048560: one launch row of 16-channel chunks)");
+  GOL_RASTER_CHECK_DIMS((uint64_t)C * 4ull, "image too large (32-bit byte offsets inside a view: H * W * C * 4 bytes)");
   if (B == 0) return GOL_OK;
   GOL_REQUIRE(tile_bins && background && out_img && final_Ts && final_idx, "null pointer");
   GOL_REQUIRE(capacity == 0 || sorted_ids, "null sorted_ids");
@@ -438,31 +379,18 @@ extern "C" int gol_rasterize_nd_fwd(int B, int N, int C, int img_h, int img_w, i
   int ppl = pixels_per_lane;
   if (ppl == 0) gol_raster_plan(B, &ppl);
   const int tiles_x = (img_w + 15) / 16, tiles_y = (img_h + 15) / 16;
-  const unsigned gx = 8 * ((tiles_y + 7) / 8) * tiles_x * B;
+  const unsigned gx = (unsigned)raster_grid(B, img_h, img_w);
   const int2* bins = reinterpret_cast<const int2*>(tile_bins);
   hipStream_t s = (hipStream_t)stream;
-#define GOL_LAUNCH_ND_FWD(CK, NCH, CF)                                                                                  \
-  do {                                                                                                                  \
-    if (ppl == 2)                                                                                                       \
-      raster_nd_fwd_kernel<CK, 2><<<dim3(gx, NCH), 128, 0, s>>>(N, C, CF, img_h, img_w, tiles_x, tiles_y, bins,         \
-                                                                sorted_ids, capacity, records, colors, background,      \
-                                                                out_img, final_Ts, final_idx, B);                       \
-    else                                                                                                                \
-      raster_nd_fwd_kernel<CK, 1><<<dim3(gx, NCH), 256, 0, s>>>(N, C, CF, img_h, img_w, tiles_x, tiles_y, bins,         \
-                                                                sorted_ids, capacity, records, colors, background,      \
-                                                                out_img, final_Ts, final_idx, B);                       \
-  } while (0)
-  const NdPlan pl = nd_plan(C);
-  if (pl.n16 > 0) GOL_LAUNCH_ND_FWD(16, pl.n16, 0);
-  switch (pl.tail) {
-    case 0: break;
-    case 1: GOL_LAUNCH_ND_FWD(1, 1, pl.tail_first); break;
-    case 2: GOL_LAUNCH_ND_FWD(2, 1, pl.tail_first); break;
-    case 4: GOL_LAUNCH_ND_FWD(4, 1, pl.tail_first); break;
-    case 8: GOL_LAUNCH_ND_FWD(8, 1, pl.tail_first); break;
-    default: GOL_REQUIRE(false, "no kernel instance for this chunk width");
-  }
-#undef GOL_LAUNCH_ND_FWD
+  const bool covered = for_nd_launches(C, [&](auto ck_c, int n_chunks, int c_first) {
+    with_ppl(ppl, [&](auto ppl_c) {
+      constexpr int CK = decltype(ck_c)::value, PPL = decltype(ppl_c)::value;
+      raster_nd_fwd_kernel<CK, PPL><<<dim3(gx, n_chunks), 64 * Pix<PPL>::kWaves, 0, s>>>(
+          N, C, c_first, img_h, img_w, tiles_x, tiles_y, bins, sorted_ids, capacity, records, colors, background, out_img,
+          final_Ts, final_idx, B);
+    });
+  });
+  GOL_REQUIRE(covered, "no kernel instance for this chunk width");
   GOL_CHECK_LAUNCH();
   return GOL_OK;
 }
@@ -472,33 +400,26 @@ extern "C" int gol_rasterize_nd_bwd(int B, int N, int C, int img_h, int img_w, i
                                     const float* background, const float* final_Ts, const int32_t* final_idx,
                                     const float* v_out_img, const float* v_out_alpha, float* v_xy, float* v_conic,
                                     float* v_colors, float* v_opacity, void* stream) {
-  GOL_ND_CHECK();
+  GOL_REQUIRE(C >= 1, "C >= 1 colour channels");
+  GOL_REQUIRE(C <= 16 * 65535, "too many colour channels (at most 1048560: one launch row of 16-channel chunks)");
+  GOL_RASTER_CHECK_DIMS((uint64_t)C * 4ull, "image too large (32-bit byte offsets inside a view: H * W * C * 4 bytes)");
   if (B == 0 || N == 0 || capacity == 0) return GOL_OK;
   GOL_REQUIRE(tile_bins && sorted_ids && background && final_Ts && final_idx, "null pointer");
   GOL_REQUIRE(v_out_img, "null v_out_img");
   GOL_REQUIRE(records && colors, "null Gaussian records / colors");
   GOL_REQUIRE(v_xy && v_conic && v_colors && v_opacity, "null gradient output");
   const int tiles_x = (img_w + 15) / 16, tiles_y = (img_h + 15) / 16;
-  const unsigned gx = 8 * ((tiles_y + 7) / 8) * tiles_x * B;
+  const unsigned gx = (unsigned)raster_grid(B, img_h, img_w);
   const int2* bins = reinterpret_cast<const int2*>(tile_bins);
   hipStream_t s = (hipStream_t)stream;
   // two pixels per lane (as the 3-channel backward): the per-visit wave sums are paid once per 128 pixels
-#define GOL_LAUNCH_ND_BWD(CK, NCH, CF)                                                                                  \
-  raster_nd_bwd_kernel<CK, 2><<<dim3(gx, NCH), 128, 0, s>>>(N, C, CF, img_h, img_w, tiles_x, tiles_y, bins, sorted_ids, \
-                                                            capacity, records, colors, background, final_Ts, final_idx, \
-                                                            v_out_img, v_out_alpha, v_xy, v_conic, v_colors, v_opacity, \
-                                                            B)
-  const NdPlan pl = nd_plan(C);
-  if (pl.n16 > 0) GOL_LAUNCH_ND_BWD(16, pl.n16, 0);
-  switch (pl.tail) {
-    case 0: break;
-    case 1: GOL_LAUNCH_ND_BWD(1, 1, pl.tail_first); break;
-    case 2: GOL_LAUNCH_ND_BWD(2, 1, pl.tail_first); break;
-    case 4: GOL_LAUNCH_ND_BWD(4, 1, pl.tail_first); break;
-    case 8: GOL_LAUNCH_ND_BWD(8, 1, pl.tail_first); break;
-    default: GOL_REQUIRE(false, "no kernel instance for this chunk width");
-  }
-#undef GOL_LAUNCH_ND_BWD
+  const bool covered = for_nd_launches(C, [&](auto ck_c, int n_chunks, int c_first) {
+    constexpr int CK = decltype(ck_c)::value;
+    raster_nd_bwd_kernel<CK, 2><<<dim3(gx, n_chunks), 128, 0, s>>>(
+        N, C, c_first, img_h, img_w, tiles_x, tiles_y, bins, sorted_ids, capacity, records, colors, background, final_Ts,
+        final_idx, v_out_img, v_out_alpha, v_xy, v_conic, v_colors, v_opacity, B);
+  });
+  GOL_REQUIRE(covered, "no kernel instance for this chunk width");
   GOL_CHECK_LAUNCH();
   return GOL_OK;
 }
