@@ -26,7 +26,7 @@ _SYMBOLS = [
     "gol_shadow_pcf", "gol_imgtail_partial_floats", "gol_imgtail_fwd", "gol_imgtail_bwd", "gol_mvp_shadow_march", "gol_mesh_raster_workspace_bytes", "gol_mesh_raster",
     "gol_mesh_render_fwd", "gol_mesh_render_bwd", "gol_mesh_render_edge_bwd",
     "gol_vert_normals_fwd", "gol_vert_normals_bwd", "gol_values_to_uv_fwd", "gol_values_to_uv_bwd", "gol_uvgeom_fwd",
-    "gol_uvgeom_bwd",
+    "gol_uvgeom_bwd", "gol_lbs_skeleton_fwd", "gol_lbs_skeleton_bwd", "gol_lbs_skin_fwd", "gol_lbs_skin_bwd",
 ]
 
 

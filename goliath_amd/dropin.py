@@ -5,6 +5,7 @@
     dropin.patch_rgca()           # optional: fused shading tail + batched, sync-free render
     dropin.patch_light_decorator()  # optional: the env-relight driver hands over ONE shared pyramid (config 2)
     dropin.patch_geometry()       # optional: GeometryModule.to_uv / .vn and the decoder's postex / tn on the uvgeom kernels
+    dropin.patch_lbs()            # optional: LinearBlendSkinning / LBSModule.pose on the fused skeleton + skinning kernels
 
 `install()` registers the module names the reference imports for its native code:
     gsplat            project_gaussians, rasterize_gaussians   (ca_code/utils/render_gsplat.py:10-11)
@@ -63,6 +64,26 @@ def patch_geometry(geom_module=None):
     geom_module.GeometryModule.to_uv = uvgeom.geometry_to_uv
     geom_module.GeometryModule.vn = uvgeom.geometry_vn
     return geom_module
+
+
+def patch_lbs(lbs_module=None):
+    """Rebind `LinearBlendSkinning.forward`, `.compute_rigid_transforms`, `.compute_rigid_transforms_matrix` and
+    `LBSModule.pose` / `.template_pose` (ca_code/utils/lbs.py:151-169, 308-337, 725-731, 741-745) to the fused HIP operators
+    of goliath_amd.lbs (gol_lbs_skeleton_* / gol_lbs_skin_*: no per-joint host sync, two launches forward, at most four
+    backward, graph-capturable, bitwise reproducible).  The packed skeleton is built lazily from the module's own buffers
+    and rebuilt when their device or shape changes.  Left alone by decision: `unpose` / `unskinning` (body models, out of
+    scope per SURVEY section 2) and `compute_root_rigid_transform`.  Idempotent.  Returns the patched module."""
+    from . import lbs
+
+    if lbs_module is None:
+        import ca_code.utils.lbs as lbs_module
+    cls = lbs_module.LinearBlendSkinning
+    cls.forward = lbs.lbs_forward
+    cls.compute_rigid_transforms = lbs.lbs_compute_rigid_transforms
+    cls.compute_rigid_transforms_matrix = lbs.lbs_compute_rigid_transforms_matrix
+    lbs_module.LBSModule.pose = lbs.lbs_module_pose
+    lbs_module.LBSModule.template_pose = lbs.lbs_module_template_pose
+    return lbs_module
 
 
 def _shared_mipmap(self, bsize, device, scale=1.0):

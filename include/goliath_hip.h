@@ -671,6 +671,50 @@ int gol_uvgeom_bwd(int B, int V, int F, int S, int T, int I, const float* verts,
                    const int32_t* vt_slot, float vn_eps, float norm_eps, const float* vn, const float* g_postex,
                    const float* g_tn, float* item_sums, float* g_s, float* g_verts, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * lbs: skeleton solve and linear blend skinning, forward and backward (csrc/lbs.hip).  Replaces the reference's per-frame
+ * PyTorch of ca_code/utils/lbs.py as called by URHand (ca_code/models/urhand.py:767) and hand_mvp / hand_teacher_mvp
+ * (ca_code/models/hand_mvp.py:390).  The constants are packed once by goliath_amd.lbs.Skeleton (int32 unless stated):
+ *   parents[J] (-1 = root, a parent's index is smaller than its child's); level_start[L+1], level_joints[J]: the joints
+ *   by tree level; child_start[J+1], child_slot[]: joint -> children, ascending; bind_inv[J,8] (double): bt, br, bs of
+ *   states_to_matrix (lbs.py:392-394); transform[7J,P] and its transpose transform_t[P,7J], transform_offsets[7J],
+ *   P = NP + NS (lbs.py:39-46); joint_offset[J,3], joint_rotation[J,4] (xyzw); skin_indices, skin_weights [V,K];
+ *   jv_slot[E]: the (vertex, slot) pairs with a non-zero weight grouped by joint, slot = vertex * K + k, ascending per
+ *   joint; item_start[I+1]: every joint's run cut into items of at most 64 entries; ji_start[J+1]: a joint's items.
+ * gol_lbs_skeleton_fwd: poses[B,NP] and scales (row b at scales + b * scales_stride; stride 0 = one row for all views)
+ *   -> states[B,J,8] (translation, rotation xyzw, scale: solve_skeleton_state, lbs.py:340-385, with Quaternion.batchFromXYZ's
+ *   half angles, quaternion.py:285-320) and mats[B,J,3,4] = states_to_matrix(bind_state, states) (lbs.py:388-429).  Either
+ *   output may be NULL.  One workgroup per view, the arithmetic in double.
+ * gol_lbs_skeleton_bwd: g_states, g_mats (either may be NULL = zero) -> g_poses[B,NP], g_scales[B,NS] (either may be
+ *   NULL), every element written.
+ * gol_lbs_skin_fwd: out[B,V,3] = (sum_k w_k mats[idx_k] [x,1]) * global_scaling with x = verts + template_verts
+ *   (skinning, lbs.py:226-254, between the two lines of LBSModule.pose, lbs.py:725-731).  verts is [B,V,3], or [V,3]
+ *   shared by the views with verts_batched = 0 (lbs.py:331-334); template_verts[V,3] and global_scaling[3] may be NULL.
+ *   A slot of weight 0 contributes nothing, whatever its index.
+ * gol_lbs_skin_bwd: g_out[B,V,3] -> g_verts[B,V,3] (the gradient of x) and g_mats[B,J,3,4], every element written; either
+ *   may be NULL; item_sums[B,I,12] (double) is scratch.
+ * No atomics: every sum has a fixed order and all outputs are bitwise reproducible.  No host sync, no allocation.
+ * ---------------------------------------------------------------------------------------- */
+int gol_lbs_skeleton_fwd(int B, int J, int NP, int NS, int L, const float* poses, const float* scales, int scales_stride,
+                         const float* transform_t, const float* transform_offsets, const float* joint_offset,
+                         const float* joint_rotation, const double* bind_inv, const int32_t* parents,
+                         const int32_t* level_start, const int32_t* level_joints, float* states, float* mats,
+                         void* stream);
+int gol_lbs_skeleton_bwd(int B, int J, int NP, int NS, int L, const float* poses, const float* scales, int scales_stride,
+                         const float* transform, const float* transform_t, const float* transform_offsets,
+                         const float* joint_offset, const float* joint_rotation, const double* bind_inv,
+                         const int32_t* parents, const int32_t* level_start, const int32_t* level_joints,
+                         const int32_t* child_start, const int32_t* child_slot, const float* g_states,
+                         const float* g_mats, float* g_poses, float* g_scales, void* stream);
+int gol_lbs_skin_fwd(int B, int V, int J, int K, const float* mats, const float* verts, int verts_batched,
+                     const float* template_verts, const float* global_scaling, const int32_t* skin_indices,
+                     const float* skin_weights, float* out, void* stream);
+int gol_lbs_skin_bwd(int B, int V, int J, int K, int E, int I, const float* mats, const float* verts, int verts_batched,
+                     const float* template_verts, const float* global_scaling, const int32_t* skin_indices,
+                     const float* skin_weights, const int32_t* item_start, const int32_t* jv_slot,
+                     const int32_t* ji_start, const float* g_out, double* item_sums, float* g_verts, float* g_mats,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
