@@ -27,6 +27,7 @@ _SYMBOLS = [
     "gol_mesh_render_fwd", "gol_mesh_render_bwd", "gol_mesh_render_edge_bwd",
     "gol_vert_normals_fwd", "gol_vert_normals_bwd", "gol_values_to_uv_fwd", "gol_values_to_uv_bwd", "gol_uvgeom_fwd",
     "gol_uvgeom_bwd", "gol_lbs_skeleton_fwd", "gol_lbs_skeleton_bwd", "gol_lbs_skin_fwd", "gol_lbs_skin_bwd",
+    "gol_optim_chunk_elems", "gol_optim_grad_stats", "gol_optim_finalize", "gol_optim_adam_step",
 ]
 
 
@@ -130,4 +131,5 @@ def call(fn_name, *args):
 
 c_int = ctypes.c_int
 c_float = ctypes.c_float
+c_double = ctypes.c_double
 c_i64 = ctypes.c_int64

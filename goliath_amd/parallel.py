@@ -368,3 +368,13 @@ def finish_scrub_and_clip(sync: "GradSync", params: Iterable[torch.nn.Parameter]
     for p in params:
         p.grad.mul_(scale.to(p.grad.device))
     return norm
+
+
+def finish_and_step(sync: "GradSync", optimizer: torch.optim.Optimizer):
+    """`finish_scrub_and_clip` and `optimizer.step()` in one, for an optimizer that scrubs and clips itself
+    (goliath_amd.optim.Adam / AdamW with max_norm and scrub_nonfinite): finish the gradient exchange, then one fused step
+    over the averaged gradients, which are views into the communication buckets.  The norm before clipping is
+    `optimizer.last_grad_norm`, a device scalar."""
+    if sync is not None:
+        sync.finish()
+    return optimizer.step()

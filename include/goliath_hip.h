@@ -715,6 +715,47 @@ int gol_lbs_skin_bwd(int B, int V, int J, int K, int E, int I, const float* mats
                      const int32_t* ji_start, const float* g_out, double* item_sums, float* g_verts, float* g_mats,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * optim: gradient scrub, global-norm clip and the Adam / AdamW step over all parameter tensors (csrc/optim.hip).
+ * Replaces the tail of the reference's training iteration, ca_code/utils/train.py:209-215: the two boolean-mask writes per
+ * parameter tensor (`p.grad.data[isnan(..)] = 0`, `[isinf(..)] = 0`: a host sync each), `clip_grad_norm_(params, 1.0)` and
+ * `optimizer.step()` of torch.optim.Adam / AdamW -- four passes over the gradients and a sync per tensor -- by one read of
+ * the gradients (grad_stats + finalize) and one pass over p, g, exp_avg, exp_avg_sq (adam_step).
+ * A SEGMENT is one float32 parameter tensor that has a gradient, described by device arrays of length n_seg: seg_p, seg_g,
+ *   seg_m, seg_v, seg_step hold 64-bit device addresses (of the parameter, its gradient, exp_avg, exp_avg_sq, all
+ *   contiguous float32 of seg_numel elements, and of the tensor's float32 step counter); seg_group is the row of `groups`.
+ * A CHUNK c is elements [chunk_off[c], chunk_off[c] + gol_optim_chunk_elems()) of segment chunk_seg[c], cut at the
+ *   segment's end; the chunks tile every segment once.  One workgroup per chunk.  16-byte accesses where a segment's
+ *   pointers are 16-byte aligned, scalar ones otherwise.
+ * groups[n_groups, GOL_OPTIM_GROUP_DOUBLES] (double): lr, beta1, beta2, eps, weight_decay, decoupled (0 = L2 decay added
+ *   to the gradient, torch.optim.Adam; 1 = p *= 1 - lr * weight_decay, AdamW), two spare.
+ * gol_optim_chunk_elems: the compile-time chunk size, in elements.
+ * gol_optim_grad_stats: partial[c] = (sum of g^2 over the chunk's FINITE entries, number of non-finite entries), both double
+ *   (train.py:209-211: a non-finite entry is 0 to the norm).
+ * gol_optim_finalize: sums the partials in index order in double (one workgroup) -> stats[0] = total_norm, stats[1] =
+ *   clip_coef = min(1, max_norm / (total_norm + 1e-6)) (clip_grad_norm_'s rule, train.py:212), nonfinite[0] = the count.
+ *   max_norm = +inf: no clipping (clip_coef = 1).
+ * gol_optim_adam_step: first, per segment, step += 1 on the device and the step's constants into seg_coef[n_seg,8]
+ *   (scratch); then per element g = isfinite(g) ? g : 0 (GOL_OPTIM_SCRUB), g *= stats[1] (GOL_OPTIM_CLIP), the cleaned g
+ *   stored (GOL_OPTIM_WRITE_BACK: the post-state of train.py:209-212), and torch's single-tensor Adam in its operation
+ *   order (train.py:215).  stats may be NULL without GOL_OPTIM_CLIP.  Any other flag (amsgrad, maximize, steps kept on
+ *   the host) returns GOL_ERR_UNSUPPORTED.
+ * No float atomics: bitwise reproducible.  No host sync, no allocation: a whole step captures as a graph.
+ * ---------------------------------------------------------------------------------------- */
+#define GOL_OPTIM_GROUP_DOUBLES 8
+#define GOL_OPTIM_SCRUB 1
+#define GOL_OPTIM_CLIP 2
+#define GOL_OPTIM_WRITE_BACK 4
+int gol_optim_chunk_elems(void);
+int gol_optim_grad_stats(int n_chunks, int n_seg, const int32_t* chunk_seg, const int64_t* chunk_off, const int64_t* seg_g,
+                         const int64_t* seg_numel, double* partial, void* stream);
+int gol_optim_finalize(int n_chunks, const double* partial, double max_norm, double* stats, int64_t* nonfinite,
+                       void* stream);
+int gol_optim_adam_step(int n_chunks, int n_seg, int n_groups, const int32_t* chunk_seg, const int64_t* chunk_off,
+                        const int64_t* seg_p, const int64_t* seg_g, const int64_t* seg_m, const int64_t* seg_v,
+                        const int64_t* seg_step, const int64_t* seg_numel, const int32_t* seg_group, const double* groups,
+                        const double* stats, float* seg_coef, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
