@@ -130,10 +130,12 @@ __device__ __forceinline__ float gol_readlane63(float v) {
 // A Gaussian (centre g, conic a,b,c, opacity op) contributes at pixel p only if
 //   op * exp(-sigma(p)) >= 1/255  <=>  sigma(p) = 0.5 d^T C d <= ln(255 op) =: tau     
 // gol_alpha_tau returns a slightly inflated tau (conservative against rounding; < 0 means "never").
+// k == 1 is still "reachable": the opacity (float)(1.f / 255.f) gives 255.f * op == 1.f exactly, and at a pixel centre that
+// coincides with the Gaussian's centre (sigma == 0) alpha = op is not below the rasterizer's 1/255 cut -- gsplat composites it.
 __device__ __forceinline__ float gol_alpha_tau(float op) {
   _Pragma("clang fp contract(on)")
   const float k = 255.f * op;
-  return (k > 1.f) ? __logf(k) * 1.001f + 1e-3f : -1.f;
+  return (k >= 1.f) ? __logf(k) * 1.001f + 1e-3f : -1.f;
 }
 // minimum of sigma over the axis-aligned rectangle [x0,x1] x [y0,y1] (exact: the quadratic is convex,
 // so the minimum is 0 inside or lies on one of the four edges)

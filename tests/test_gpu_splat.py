@@ -98,11 +98,17 @@ def test_bin_sort_matches_oracle_exactly():
     I3 = int(ws3.n_isect[0])
     assert 0 < I3 < I
     b3, ids3 = ws3.tile_bins[0].cpu(), ws3.sorted_ids[0].cpu()
-    for t in range(0, T, 7):
+    from binning_cases import prune_reference
+
+    live = prune_reference(xys, radii, conics, opac.cpu(), s["H"], s["W"], (ids, bins))   # float64, per pair of `ids`
+    assert 0 < int(live.sum()) < I
+    for t in range(T):
         full = ids[bins[t, 0]:bins[t, 1]].tolist()
         sub = ids3[b3[t, 0]:b3[t, 1]].tolist()
         it = iter(full)
         assert all(g in it for g in sub), t  # order-preserving subsequence
+        must = {g for g, v in zip(full, live[bins[t, 0]:bins[t, 1]]) if v}
+        assert must <= set(sub), t           # ... that keeps every Gaussian some pixel centre of the tile can see
 
 
 @pytest.mark.parametrize("N", [2, 63, 200, 256, 257, 500, 513, 1000, 1024, 1025, 2000, 2048, 2049, 3500, 4096, 4097, 6000,
