@@ -28,6 +28,7 @@ _SYMBOLS = [
     "gol_vert_normals_fwd", "gol_vert_normals_bwd", "gol_values_to_uv_fwd", "gol_values_to_uv_bwd", "gol_uvgeom_fwd",
     "gol_uvgeom_bwd", "gol_lbs_skeleton_fwd", "gol_lbs_skeleton_bwd", "gol_lbs_skin_fwd", "gol_lbs_skin_bwd",
     "gol_optim_chunk_elems", "gol_optim_grad_stats", "gol_optim_finalize", "gol_optim_adam_step",
+    "gol_regloss_chunk_elems", "gol_regloss_fwd", "gol_regloss_bwd", "gol_backlit_fwd", "gol_backlit_bwd",
 ]
 
 

@@ -120,10 +120,16 @@ def patch_light_decorator(decorator_module=None):
     return decorator_module
 
 
-def patch_losses(registry_module=None):
+REGULARIZER_LOSSES = ("bound_primscale", "negcolor", "l2_reg", "list_l1_reg", "backlit_reg", "alphaprior", "mask_l1")
+
+
+def patch_losses(registry_module=None, regularizers=False):
     """Re-register the image losses of the reference's loss registry (ca_code/loss/registry.py:59-79; rgb_l1 and
     rgb_ssim, ca_code/loss/__init__.py:391-411, 478-494) with the fused HIP versions, so a `ModularLoss` built from the
-    unchanged config picks them up.  Call after `import ca_code.loss` and before constructing the loss."""
+    unchanged config picks them up.  Call after `import ca_code.loss` and before constructing the loss.
+    regularizers=True also re-registers the per-Gaussian regularisers and their kin (REGULARIZER_LOSSES,
+    ca_code/loss/__init__.py:450-453, 560-600, 609-622) with the gol_regloss_* / gol_backlit_* operators of
+    goliath_amd.losses; every other entry of the registry stays the reference's."""
     from . import losses
 
     if registry_module is None:
@@ -135,6 +141,9 @@ def patch_losses(registry_module=None):
 
     for name, fn in (("rgb_l1", losses.rgb_l1), ("rgb_ssim", losses.rgb_ssim)):
         registry_module.loss_registry[name] = factory(fn)
+    if regularizers:
+        for name in REGULARIZER_LOSSES:
+            registry_module.loss_registry[name] = factory(getattr(losses, name))
     return registry_module
 
 

@@ -2,13 +2,19 @@
 
   rgb_l1(preds, targets, ...)   <- ca_code/loss/__init__.py:391-411  (same signature / keys)
   l1_image(pred, target, mask)  the fused op: one read pass forward, one read + one write pass backward
+
+and the per-Gaussian regularisers (csrc/regloss.hip): one read pass forward, one read + one write pass backward each
+  penalty_mean(x, kind, p0, p1)  mean of an elementwise penalty (BOUND, NEG_SQ, SQ, ABS, ALPHAPRIOR)
+  backlit(color, cos_weight)     sum(w * relu(color)) / (1 + sum(w)), w = relu(-cos_weight)^2
+  bound_primscale, negcolor, l2_reg, list_l1_reg, backlit_reg, alphaprior, mask_l1
+                                <- ca_code/loss/__init__.py:560-600, 609-622, 450-453  (same signatures / keys)
 """
 from typing import Optional
 
 import torch
 
 from . import _lib
-from ._lib import c_int, fptr, stream_ptr
+from ._lib import c_float, c_i64, c_int, fptr, ptr, stream_ptr
 
 
 class _L1(torch.autograd.Function):
@@ -123,3 +129,134 @@ def rgb_ssim(preds, targets, src_key: str = "rendered_rgb", tgt_key: str = "imag
     if mask is None or normalize_mask:
         return 1.0 - ssim_image(preds[src_key], targets[tgt_key], None if mask is None else mask.float())
     return 1.0 - ssim_image(mask * preds[src_key], mask * targets[tgt_key])
+
+
+# ---- per-Gaussian regularisers (gol_regloss_*, gol_backlit_*) ---------------------------------------------------------
+BOUND, NEG_SQ, SQ, ABS, ALPHAPRIOR = range(5)   # gol_regloss_kind of include/goliath_hip.h
+
+
+def regloss_chunk_elems():
+    return _lib.load().gol_regloss_chunk_elems()
+
+
+class _Penalty(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kind, p0, p1):
+        n = x.numel()
+        nb = -(-n // regloss_chunk_elems())
+        partial = torch.empty(nb, device=x.device, dtype=torch.float64)
+        with _lib.device_guard(x.device):
+            _lib.call("gol_regloss_fwd", c_int(kind), c_i64(n), c_float(p0), c_float(p1), fptr(x),
+                      ptr(partial, torch.float64), stream_ptr())
+        ctx.save_for_backward(x)
+        ctx.args = (kind, p0, p1)
+        return (partial.sum() / n).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        (x,) = ctx.saved_tensors
+        kind, p0, p1 = ctx.args
+        n = x.numel()
+        out = torch.empty_like(x)
+        gs = (g.to(torch.float32) / n).reshape(1).contiguous()
+        with _lib.device_guard(x.device):
+            _lib.call("gol_regloss_bwd", c_int(kind), c_i64(n), c_float(p0), c_float(p1), fptr(x), fptr(gs), fptr(out),
+                      stream_ptr())
+        return out, None, None, None
+
+
+def penalty_mean(x: torch.Tensor, kind: int, p0: float = 0.0, p1: float = 0.0) -> torch.Tensor:
+    """mean(f(x)) over all elements of x for the penalty `kind` (BOUND: p0 = min, p1 = max; the others read no parameter);
+    f and f' as listed at gol_regloss_fwd in include/goliath_hip.h.  A float32 scalar, differentiable in x."""
+    if not x.is_cuda:
+        raise _lib.GoliathHipError("penalty_mean needs CUDA(HIP) tensors; there is no CPU path")
+    if x.numel() == 0:
+        raise ValueError("penalty_mean of an empty tensor")
+    return _Penalty.apply(x.to(torch.float32).contiguous(), int(kind), float(p0), float(p1))
+
+
+class _Backlit(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, color, cosw):
+        C = color.shape[-1]
+        M = cosw.numel()
+        nb = -(-M // (regloss_chunk_elems() // 4))
+        partial = torch.empty(nb, 2, device=color.device, dtype=torch.float64)
+        with _lib.device_guard(color.device):
+            _lib.call("gol_backlit_fwd", c_i64(M), c_int(C), fptr(color), fptr(cosw), ptr(partial, torch.float64),
+                      stream_ptr())
+        num, den = partial.sum(0).unbind(0)
+        denom = 1.0 + den
+        ctx.save_for_backward(color, cosw, denom)
+        return (num / denom).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        color, cosw, denom = ctx.saved_tensors
+        out = torch.empty_like(color)
+        gs = (g.to(torch.float64) / denom).to(torch.float32).reshape(1).contiguous()
+        with _lib.device_guard(color.device):
+            _lib.call("gol_backlit_bwd", c_i64(cosw.numel()), c_int(color.shape[-1]), fptr(color), fptr(cosw), fptr(gs),
+                      fptr(out), stream_ptr())
+        return out, None
+
+
+def backlit(color: torch.Tensor, cos_weight: torch.Tensor) -> torch.Tensor:
+    """sum(w * relu(color)) / (1 + sum(w)) with w = relu(-cos_weight)^2: color [..., C], cos_weight [..., 1] (or [...]),
+    one weight per colour row, counted once in the denominator.  Differentiable in color only: the model builds
+    cos_weight under no_grad, and one that requires grad raises."""
+    if not (color.is_cuda and cos_weight.is_cuda):
+        raise _lib.GoliathHipError("backlit needs CUDA(HIP) tensors; there is no CPU path")
+    if cos_weight.requires_grad:
+        raise ValueError("backlit: cos_weight receives no gradient (build it under no_grad, or detach it)")
+    if color.numel() == 0:
+        raise ValueError("backlit of an empty tensor")
+    if tuple(cos_weight.shape) not in (tuple(color.shape[:-1]) + (1,), tuple(color.shape[:-1])):
+        raise ValueError(f"backlit: cos_weight {tuple(cos_weight.shape)} does not give one weight per row of color "
+                         f"{tuple(color.shape)}")
+    return _Backlit.apply(color.to(torch.float32).contiguous(), cos_weight.to(torch.float32).contiguous())
+
+
+def bound_primscale(preds, batch=None, key: str = "primscale_preclip", min_scale: float = 0.1, max_scale: float = 20.0):
+    """Same semantics as the reference's bound_primscale (ca_code/loss/__init__.py:560-573)."""
+    return penalty_mean(preds[key], BOUND, min_scale, max_scale)
+
+
+def negcolor(preds, batch=None, key: str = "diff_color"):
+    """Same semantics as the reference's negcolor (ca_code/loss/__init__.py:576-578)."""
+    return penalty_mean(preds[key], NEG_SQ)
+
+
+def l2_reg(preds, batch=None, key: str = "spec_dnml"):
+    """Same semantics as the reference's l2_reg (ca_code/loss/__init__.py:581-583)."""
+    return penalty_mean(preds[key], SQ)
+
+
+def list_l1_reg(preds, batch=None, key: str = "spec_dnml"):
+    """Same semantics as the reference's list_l1_reg (ca_code/loss/__init__.py:585-590): the sum of the terms' means."""
+    loss = 0
+    for term in preds[key]:
+        loss = loss + penalty_mean(term, ABS)
+    return loss
+
+
+def backlit_reg(preds, batch=None, key: str = "color_rand", cos_key: str = "cos_weight"):
+    """Same semantics as the reference's backlit_reg (ca_code/loss/__init__.py:592-600)."""
+    return backlit(preds[key], preds[cos_key])
+
+
+def alphaprior(preds, batch=None, key: str = "alpha"):
+    """Same semantics as the reference's alphaprior (ca_code/loss/__init__.py:609-622)."""
+    return penalty_mean(preds[key], ALPHAPRIOR)
+
+
+def mask_l1(preds, targets, src_key: str = "rendered_mask", tgt_key: str = "image_mask"):
+    """Same semantics as the reference's mask_l1 (ca_code/loss/__init__.py:450-453): l1_image without a mask."""
+    pred, target = preds[src_key], targets[tgt_key]
+    if pred.dim() < 2:
+        pred, target = pred.reshape(1, 1, -1), target.reshape(1, 1, -1)
+    return l1_image(pred, target.expand_as(pred) if target.shape != pred.shape else target)

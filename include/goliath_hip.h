@@ -756,6 +756,46 @@ int gol_optim_adam_step(int n_chunks, int n_seg, int n_groups, const int32_t* ch
                         const int64_t* seg_step, const int64_t* seg_numel, const int32_t* seg_group, const double* groups,
                         const double* stats, float* seg_coef, int flags, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * regloss: the per-Gaussian regularisers of the training loss (csrc/regloss.hip).  Each replaces a chain of ATen
+ * launches over a [B,N,3] tensor by one read pass forward and one read + one write pass backward.
+ * A CHUNK is gol_regloss_chunk_elems() consecutive elements (flat penalties) or a quarter as many rows (backlit); one
+ * workgroup per chunk, 16-byte accesses on full chunks of 16-byte aligned tensors, scalar ones otherwise.
+ * gol_regloss_fwd: partial[cdiv(n, chunk)] (double) = per-chunk sums of f(x[i]); the caller forms sum(partial) / n.
+ * gol_regloss_bwd: g_x[i] = g_scale[0] * f'(x[i]) for every i; g_scale is a DEVICE scalar (upstream gradient / n).
+ *   kind                    f(x)                                                     replaces ca_code/loss/__init__.py
+ *   GOL_REGLOSS_BOUND       x < p0 ? 1 / max(x, 1e-7) : (x > p1 ? (x - p1)^2 : 0)    :560-573 bound_primscale (p0 = min_scale,
+ *                           f' = x < p0 ? (x >= 1e-7 ? -1/x^2 : 0) : (x > p1 ? 2 (x - p1) : 0)              p1 = max_scale)
+ *   GOL_REGLOSS_NEG_SQ      min(x, 0)^2,  f' = 2 min(x, 0)                           :576-578 negcolor
+ *   GOL_REGLOSS_SQ          x^2,  f' = 2 x                                           :581-583 l2_reg
+ *   GOL_REGLOSS_ABS         |x|,  f' = sign(x), 0 at 0                               :585-590 list_l1_reg (one call per term)
+ *   GOL_REGLOSS_ALPHAPRIOR  log(0.1 + x) + log(1.1 - x) + 2.20727                    :609-622 alphaprior
+ *                           f' = 1 / (0.1 + x) - 1 / (1.1 - x)
+ *   (p0, p1 are read by GOL_REGLOSS_BOUND only.)  float32 arithmetic in torch's operation order, IEEE division, accurate
+ *   logf; only finite inputs are specified.
+ * gol_backlit_fwd / _bwd: ca_code/loss/__init__.py:592-600 backlit_reg.  color[m,c], cosw[m]; w = max(-cosw, 0)^2.
+ *   fwd: partial[cdiv(m, chunk / 4), 2] (double) = per-chunk (sum_c w * max(color, 0), sum w) -- a row's w counts ONCE; the
+ *   caller forms num / (1 + den).  bwd: g_color[r,j] = g_scale[0] * w[r] * (color[r,j] > 0), g_scale = upstream / (1 + den)
+ *   on the device.  cosw receives no gradient.  Any c >= 1; c == 3 is the 16-byte path (a lane owns four rows).
+ * An unknown kind, a negative count or a null pointer with a positive count returns GOL_ERR_INVALID_ARG; a count of 0
+ * returns GOL_OK without a launch.  Fixed-order sums in double, no float atomics: bitwise reproducible.  No host sync, no
+ * allocation: captures as a linear graph.
+ * ---------------------------------------------------------------------------------------- */
+typedef enum {
+  GOL_REGLOSS_BOUND = 0,
+  GOL_REGLOSS_NEG_SQ = 1,
+  GOL_REGLOSS_SQ = 2,
+  GOL_REGLOSS_ABS = 3,
+  GOL_REGLOSS_ALPHAPRIOR = 4
+} gol_regloss_kind;
+int gol_regloss_chunk_elems(void);
+int gol_regloss_fwd(int kind, int64_t n, float p0, float p1, const float* x, double* partial, void* stream);
+int gol_regloss_bwd(int kind, int64_t n, float p0, float p1, const float* x, const float* g_scale, float* g_x,
+                    void* stream);
+int gol_backlit_fwd(int64_t m, int c, const float* color, const float* cosw, double* partial, void* stream);
+int gol_backlit_bwd(int64_t m, int c, const float* color, const float* cosw, const float* g_scale, float* g_color,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
