@@ -122,6 +122,23 @@ __device__ __forceinline__ float gol_wave_sum_to_lane63(float v) {
   return gol_add_row_bcast31(v);            // row_bcast:31 into rows 2 and 3
 }
 
+// The same ladder on doubles, in the same order.  v + (the DPP-selected lane's v, 0 where the selection leaves the row /
+// the row is masked off): the two halves of the double travel as two 32-bit DPP moves.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double gol_dpp_add0(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
+  return v + __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double gol_wave_sum_to_lane63(double v) {
+  v = gol_dpp_add0<0x111, 0xf>(v);          // row_shr:1
+  v = gol_dpp_add0<0x112, 0xf>(v);          // row_shr:2
+  v = gol_dpp_add0<0x114, 0xf>(v);          // row_shr:4
+  v = gol_dpp_add0<0x118, 0xf>(v);          // row_shr:8   -> lane 15 of each row = the row's sum
+  v = gol_dpp_add0<0x142, 0xa>(v);          // row_bcast:15 into rows 1 and 3
+  return gol_dpp_add0<0x143, 0xc>(v);       // row_bcast:31 into rows 2 and 3
+}
+
 __device__ __forceinline__ float gol_readlane63(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }

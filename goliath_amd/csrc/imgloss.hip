@@ -5,15 +5,12 @@
 // = 8 passes over the 2048x1334x3 image per view; here the forward reads pred/target(/mask) once and
 // the backward reads them once and writes the gradient once ("losses on the image").
 // Purely HBM-bound streaming kernels, 16 B per lane.
-#include "gol_common.h"
+#include "gol_stream.h"
 
 namespace {
 
 __device__ __forceinline__ float block_sum(float v, float* s_part) {
-  v = gol_wave_sum_to_lane63(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 63) s_part[wave] = v;
-  __syncthreads();
+  gol_wave_sums_to_lds(v, s_part);
   float t = 0.f;
   if (threadIdx.x == 0) for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s_part[w];
   return t;  // valid in thread 0

@@ -25,6 +25,7 @@
 //     the v_permlane*_swap ladder (one atomic per wave per scalar, like the reference's
 //     fastAtomicAdd per warp); template gradients are scattered with hardware f32 atomics.
 #include "gol_common.h"
+#include "gol_vec3.h"
 
 namespace {
 
@@ -52,18 +53,7 @@ __device__ __forceinline__ bool window_active(unsigned w, int iter) {
 // does this lane's half keep list entry e?
 __device__ __forceinline__ bool half_keeps(int e, int lane) { return (e & (lane < 32 ? kKeepA : kKeepB)) != 0; }
 
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
-__device__ __forceinline__ V3 ld3(const float* __restrict__ p) { return V3{p[0], p[1], p[2]}; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(V3 a, V3 b) { return V3{a.x * b.x, a.y * b.y, a.z * b.z}; }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return V3{a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ float min3(V3 a) { return fminf(fminf(a.x, a.y), a.z); }
-__device__ __forceinline__ float max3(V3 a) { return fmaxf(fmaxf(a.x, a.y), a.z); }
-__device__ __forceinline__ V3 vmin(V3 a, V3 b) { return V3{fminf(a.x, b.x), fminf(a.y, b.y), fminf(a.z, b.z)}; }
-__device__ __forceinline__ V3 vmax(V3 a, V3 b) { return V3{fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z)}; }
+using namespace gol_vec3;
 
 // ---- compute_raydirs ------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void raydirs_kernel(int N, int H, int W, const float* __restrict__ viewpos,
@@ -759,6 +749,16 @@ int check_march(int N, int H, int W, int K, int TD, int TH, int TW, float stepsi
   return GOL_OK;
 }
 
+// what the five march entries share: the kernel arguments (group / alpha_only / warp keep their defaults) and the grid, one
+// 16x16-pixel workgroup (four 8x8 wave footprints) per tile and ray image
+MarchArgs march_args(int N, int H, int W, int K, int TD, int TH, int TW, float stepsize, float fadescale, float fadeexp,
+                     const float* raypos, const float* raydir, const float* tminmax, const float* nodeaabb,
+                     const float* primpos, const float* primrot, const float* primscale, const float* tplate) {
+  return MarchArgs{N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb,
+                   primpos, primrot, primscale, tplate};
+}
+dim3 march_grid(int N, int H, int W) { return dim3(gol_cdiv(W, 16), gol_cdiv(H, 16), N); }
+
 }  // namespace
 
 extern "C" int gol_raydirs_fwd(int N, int H, int W, const float* viewpos, const float* viewrot, const float* focal,
@@ -794,9 +794,9 @@ extern "C" int gol_mvp_march_fwd(int N, int H, int W, int K, const float* raypos
   if (N == 0 || H == 0 || W == 0) return GOL_OK;
   GOL_REQUIRE(raypos && raydir && tminmax && nodeaabb && primpos && primrot && primscale && tplate && rayrgba,
               "null pointer");
-  MarchArgs a{N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb,
-              primpos, primrot, primscale, tplate};
-  dim3 grid(gol_cdiv(W, 16), gol_cdiv(H, 16), N);
+  MarchArgs a = march_args(N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos,
+                           primrot, primscale, tplate);
+  const dim3 grid = march_grid(N, H, W);
   if (shadow) march_fwd_kernel<true, false><<<grid, 256, 0, (hipStream_t)stream>>>(a, rayrgba, raysat, shadow);
   else march_fwd_kernel<false, false><<<grid, 256, 0, (hipStream_t)stream>>>(a, rayrgba, raysat, shadow);
   GOL_CHECK_LAUNCH();
@@ -814,10 +814,10 @@ extern "C" int gol_mvp_march_warp_fwd(int N, int H, int W, int K, const float* r
   if (N == 0 || H == 0 || W == 0) return GOL_OK;
   GOL_REQUIRE(raypos && raydir && tminmax && nodeaabb && primpos && primrot && primscale && tplate && warp && rayrgba,
               "null pointer");
-  MarchArgs a{N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb,
-              primpos, primrot, primscale, tplate};
+  MarchArgs a = march_args(N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos,
+                           primrot, primscale, tplate);
   a.warp = warp; a.WD = WD; a.WH = WH; a.WW = WW;
-  dim3 grid(gol_cdiv(W, 16), gol_cdiv(H, 16), N);
+  const dim3 grid = march_grid(N, H, W);
   if (shadow) march_fwd_kernel<true, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, rayrgba, raysat, shadow);
   else march_fwd_kernel<false, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, rayrgba, raysat, shadow);
   GOL_CHECK_LAUNCH();
@@ -835,9 +835,10 @@ extern "C" int gol_mvp_shadow_march(int N, int group, int H, int W, int K, const
   if (N == 0 || H == 0 || W == 0) return GOL_OK;
   GOL_REQUIRE(raypos && raydir && tminmax && nodeaabb && primpos && primrot && primscale && tplate && shadow,
               "null pointer");
-  MarchArgs a{N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb,
-              primpos, primrot, primscale, tplate, group, alpha_only ? 1 : 0};
-  dim3 grid(gol_cdiv(W, 16), gol_cdiv(H, 16), N);
+  MarchArgs a = march_args(N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos,
+                           primrot, primscale, tplate);
+  a.group = group; a.alpha_only = alpha_only ? 1 : 0;
+  const dim3 grid = march_grid(N, H, W);
   march_fwd_kernel<true, false><<<grid, 256, 0, (hipStream_t)stream>>>(a, rayrgba, nullptr, shadow);
   GOL_CHECK_LAUNCH();
   return GOL_OK;
@@ -854,9 +855,9 @@ extern "C" int gol_mvp_march_bwd(int N, int H, int W, int K, const float* raypos
   if (N == 0 || H == 0 || W == 0) return GOL_OK;
   GOL_REQUIRE(raypos && raydir && tminmax && nodeaabb && primpos && primrot && primscale && tplate, "null pointer");
   GOL_REQUIRE(raysat && grad_rayrgba && grad_primpos && grad_primrot && grad_primscale && grad_tplate, "null pointer");
-  MarchArgs a{N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb,
-              primpos, primrot, primscale, tplate};
-  dim3 grid(gol_cdiv(W, 16), gol_cdiv(H, 16), N);
+  MarchArgs a = march_args(N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos,
+                           primrot, primscale, tplate);
+  const dim3 grid = march_grid(N, H, W);
   march_bwd_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(a, raysat, grad_rayrgba, grad_primpos, grad_primrot,
                                                                   grad_primscale, grad_tplate, nullptr);
   GOL_CHECK_LAUNCH();
@@ -877,10 +878,10 @@ extern "C" int gol_mvp_march_warp_bwd(int N, int H, int W, int K, const float* r
   GOL_REQUIRE(raypos && raydir && tminmax && nodeaabb && primpos && primrot && primscale && tplate && warp, "null pointer");
   GOL_REQUIRE(raysat && grad_rayrgba && grad_primpos && grad_primrot && grad_primscale && grad_tplate && grad_warp,
               "null pointer");
-  MarchArgs a{N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb,
-              primpos, primrot, primscale, tplate};
+  MarchArgs a = march_args(N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos,
+                           primrot, primscale, tplate);
   a.warp = warp; a.WD = WD; a.WH = WH; a.WW = WW;
-  dim3 grid(gol_cdiv(W, 16), gol_cdiv(H, 16), N);
+  const dim3 grid = march_grid(N, H, W);
   march_bwd_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(a, raysat, grad_rayrgba, grad_primpos, grad_primrot,
                                                                  grad_primscale, grad_tplate, grad_warp);
   GOL_CHECK_LAUNCH();

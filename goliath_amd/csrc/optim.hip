@@ -7,45 +7,20 @@
 // CU holds well over the ~50 KB in flight that the copy ceiling needs (6.3 TB/s x ~2 us / 256 CUs) at any occupancy the
 // register count leaves.  A segment whose pointers are not all 16-byte aligned (a gradient that is a view into a
 // communication bucket) takes the scalar path; a tensor's last 1-3 elements are handled by three lanes.
-// No atomics: every sum has a fixed order, so the norm, the coefficient and the step are bitwise reproducible.
-#include "gol_common.h"
+// No atomics: every sum has a fixed order (lane, then gol_block_sum of gol_stream.h: DPP ladder over the wave, LDS over the
+// waves), so the norm, the coefficient and the step are bitwise reproducible.
+#include "gol_stream.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kChunk = 4096;
-constexpr int kVecIters = kChunk / 4 / kBlock;   // float4 loads per lane and array
+using namespace gol_stream;   // f4 / gfloat / gf4 / global_floats, kBlock, kChunk, kVecIters, chunk_elems
+
 constexpr int kFinalBlock = 1024;
 constexpr int kCoef = 8;                         // floats per segment written by optim_prepare_kernel
 
 enum { kScrub = GOL_OPTIM_SCRUB, kClip = GOL_OPTIM_CLIP, kWriteBack = GOL_OPTIM_WRITE_BACK, kAllFlags = 7 };
 
-// The tensors are reached through 64-bit addresses read from the segment table; telling the compiler they are global
-// memory gives global_load / global_store (an address of unknown space costs a flat access and a wait on both counters).
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) f4 gf4;
-__device__ __forceinline__ gfloat* global_floats(int64_t addr, int64_t off) {
-  return reinterpret_cast<gfloat*>(static_cast<uintptr_t>(addr)) + off;
-}
-
 __device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
-// sum over the workgroup in a fixed order; the result is valid in thread 0
-template <int WAVES>
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, GOL_WAVE);
-  if ((threadIdx.x & (GOL_WAVE - 1)) == 0) sh[threadIdx.x / GOL_WAVE] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) t += sh[w];
-  }
-  __syncthreads();
-  return t;
-}
 
 struct Chunk {
   int seg;
@@ -61,7 +36,7 @@ __device__ __forceinline__ Chunk chunk_of(const int32_t* chunk_seg, const int64_
   c.n = 0;
   if (c.seg >= 0 && c.seg < n_seg && c.off >= 0) {
     const int64_t rem = seg_numel[c.seg] - c.off;
-    c.n = rem >= kChunk ? kChunk : (rem > 0 ? (int)rem : 0);
+    c.n = chunk_elems(rem > 0 ? rem : 0);
   }
   return c;
 }
@@ -100,8 +75,8 @@ __global__ __launch_bounds__(kBlock) void optim_grad_stats_kernel(int n_seg, con
       for (int i = threadIdx.x; i < c.n; i += kBlock) stat_add(g[i], sq, bad);
     }
   }
-  sq = block_sum<kBlock / GOL_WAVE>(sq, sh);
-  bad = block_sum<kBlock / GOL_WAVE>(bad, sh);
+  sq = gol_block_sum<double, kBlock / GOL_WAVE>(sq, sh);
+  bad = gol_block_sum<double, kBlock / GOL_WAVE>(bad, sh);
   if (threadIdx.x == 0) {
     partial[2 * (size_t)blockIdx.x] = sq;
     partial[2 * (size_t)blockIdx.x + 1] = bad;
@@ -117,8 +92,8 @@ __global__ __launch_bounds__(kFinalBlock) void optim_finalize_kernel(int n_chunk
     sq += partial[2 * (size_t)c];
     bad += partial[2 * (size_t)c + 1];
   }
-  sq = block_sum<kFinalBlock / GOL_WAVE>(sq, sh);
-  bad = block_sum<kFinalBlock / GOL_WAVE>(bad, sh);
+  sq = gol_block_sum<double, kFinalBlock / GOL_WAVE>(sq, sh);
+  bad = gol_block_sum<double, kFinalBlock / GOL_WAVE>(bad, sh);
   if (threadIdx.x == 0) {
     const double norm = sqrt(sq);
     const double coef = max_norm / (norm + 1e-6);   // clip_grad_norm_'s rule

@@ -4,60 +4,22 @@
 // One 256-thread workgroup per chunk of kChunk = 4096 floats = 4 float4 per lane; a lane issues all of its 16-byte loads
 // before the first use and a full chunk has no predicated access.  The last (partial) chunk and a base pointer that is not
 // 16-byte aligned take a scalar path that keeps each lane's elements and their order, so both paths give the same bits.
-// One workgroup per chunk, no grid-stride loop and no block cap (25 M elements are 6144 workgroups).  Every sum has a fixed order (lane, DPP ladder over the wave, LDS over the four waves) and is kept in double:
+// One workgroup per chunk, no grid-stride loop and no block cap (25 M elements are 6144 workgroups).  Every sum has a fixed
+// order (lane, then gol_block_sum of gol_stream.h: DPP ladder over the wave, LDS over the four waves) and is kept in double:
 // no float atomics, the same bits every run.  The per-element arithmetic is float32 in torch's operation order, without
 // contraction, with IEEE division and the accurate logf.
-#include "gol_common.h"
+#include "gol_stream.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kChunk = 4096;
-constexpr int kVecIters = kChunk / 4 / kBlock;   // float4 loads per lane of a flat array
+using namespace gol_stream;   // f4 / gfloat / gf4 / global_in / global_out, kBlock, kChunk, kVecIters, chunk_elems
+
 constexpr int kRows = kChunk / 4;                // backlit: rows of a chunk (C = 3: 3072 colours + 1024 weights)
 
 enum { kBound = GOL_REGLOSS_BOUND, kNegSq = GOL_REGLOSS_NEG_SQ, kSq = GOL_REGLOSS_SQ, kAbs = GOL_REGLOSS_ABS,
        kAlphaPrior = GOL_REGLOSS_ALPHAPRIOR };
-
-// the tensors are global memory: global_load / global_store instead of flat accesses
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) f4 gf4;
-__device__ __forceinline__ const gfloat* global_in(const float* p) {
-  return reinterpret_cast<const gfloat*>(reinterpret_cast<uintptr_t>(p));
-}
-__device__ __forceinline__ gfloat* global_out(float* p) { return reinterpret_cast<gfloat*>(reinterpret_cast<uintptr_t>(p)); }
-
-// v + (the DPP-selected lane's v, 0 where the selection leaves the row / the row is masked off): the two halves of the
-// double travel as two 32-bit DPP moves
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_add0(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-  return v + __hiloint2double(hi, lo);
-}
-
-// sum over the workgroup in a fixed order; the result is valid in thread 0.  The wave sum is the row_shr 1/2/4/8 +
-// row_bcast 15/31 ladder of gol_wave_sum_to_lane63, on doubles: its total lands in lane 63.
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-  v = dpp_add0<0x111, 0xf>(v);   // row_shr:1
-  v = dpp_add0<0x112, 0xf>(v);   // row_shr:2
-  v = dpp_add0<0x114, 0xf>(v);   // row_shr:4
-  v = dpp_add0<0x118, 0xf>(v);   // row_shr:8   -> lane 15 of each row = the row's sum
-  v = dpp_add0<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-  v = dpp_add0<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
-  if ((threadIdx.x & (GOL_WAVE - 1)) == GOL_WAVE - 1) sh[threadIdx.x / GOL_WAVE] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < kBlock / GOL_WAVE; ++w) t += sh[w];
-  }
-  __syncthreads();
-  return t;
-}
 
 // ---- the unary penalties: f and g_scale * f', float32 in torch's operation order -----------------------------------------
 template <int KIND>
@@ -93,18 +55,12 @@ __device__ __forceinline__ float pen_df(float x, float p0, float p1, float gs) {
   }
 }
 
-// elements of chunk blockIdx.x: 1..kChunk (the grid has exactly cdiv(n, kChunk) workgroups)
-__device__ __forceinline__ int chunk_elems(int64_t n, int64_t off) {
-  const int64_t rem = n - off;
-  return rem >= kChunk ? kChunk : (int)rem;
-}
-
 template <int KIND>
 __global__ __launch_bounds__(kBlock) void regloss_fwd_kernel(int64_t n, float p0, float p1, const float* __restrict__ x_,
                                                               double* __restrict__ partial) {
   __shared__ double sh[kBlock / GOL_WAVE];
   const int64_t off = (int64_t)blockIdx.x * kChunk;
-  const int cn = chunk_elems(n, off);
+  const int cn = chunk_elems(n - off);
   const gfloat* x = global_in(x_) + off;
   double acc = 0.0;
   if (cn == kChunk && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
@@ -126,7 +82,7 @@ __global__ __launch_bounds__(kBlock) void regloss_fwd_kernel(int64_t n, float p0
       }
     }
   }
-  acc = block_sum(acc, sh);
+  acc = gol_block_sum<double, kBlock / GOL_WAVE>(acc, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
@@ -134,7 +90,7 @@ template <int KIND>
 __global__ __launch_bounds__(kBlock) void regloss_bwd_kernel(int64_t n, float p0, float p1, const float* __restrict__ x_,
                                                               const float* __restrict__ g_scale, float* __restrict__ g_x_) {
   const int64_t off = (int64_t)blockIdx.x * kChunk;
-  const int cn = chunk_elems(n, off);
+  const int cn = chunk_elems(n - off);
   const gfloat* x = global_in(x_) + off;
   gfloat* g = global_out(g_x_) + off;
   const float gs = g_scale[0];
@@ -197,8 +153,8 @@ __global__ __launch_bounds__(kBlock) void backlit_fwd_kernel(int64_t m, int c, c
       for (int j = 0; j < c; ++j) num += (double)(w * fmaxf(row[j], 0.f));
     }
   }
-  num = block_sum(num, sh);
-  den = block_sum(den, sh);
+  num = gol_block_sum<double, kBlock / GOL_WAVE>(num, sh);
+  den = gol_block_sum<double, kBlock / GOL_WAVE>(den, sh);
   if (threadIdx.x == 0) {
     partial[2 * (size_t)blockIdx.x] = num;
     partial[2 * (size_t)blockIdx.x + 1] = den;

@@ -13,7 +13,7 @@
 //   backward  d loss/d img2[q] = g * ( conv(M0)[q] + 2 img2[q] conv(M1)[q] + img1[q] conv(M2)[q] )  (symmetric window):
 //             three separable convolutions of the saved maps, same tiling.
 // HBM per pixel and channel: fwd 8 B in (+ mask) + 12 B out, bwd 12 B + 8 B in, 4 B out; everything else is LDS.
-#include "gol_common.h"
+#include "gol_stream.h"
 
 namespace {
 
@@ -60,10 +60,7 @@ __device__ __forceinline__ Strip strip_of_block(int H, int W) {
 }
 
 __device__ __forceinline__ float block_sum(float v, float* s_part) {
-  v = gol_wave_sum_to_lane63(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 63) s_part[wave] = v;
-  __syncthreads();
+  gol_wave_sums_to_lds(v, s_part);
   return s_part[0] + s_part[1] + s_part[2] + s_part[3];
 }
 

@@ -24,24 +24,14 @@
 // Every sum has a fixed order: all results are bitwise reproducible from run to run.
 // Clamp semantics are autograd's: where a norm is below its eps the denominator is a constant in the derivative.
 #include "gol_common.h"
+#include "gol_vec3.h"
 
 namespace {
 
 constexpr float kFaceEps = 1e-5f;   // face_normals' eps (geom.py:327): vert_normals never overrides it
 constexpr int kItemRow = 16;        // lanes per item (one DPP row)
 
-struct V3 {
-  float x, y, z;
-};
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ V3 operator/(V3 a, float s) { return {a.x / s, a.y / s, a.z / s}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ float norm(V3 a) { return sqrtf(dot(a, a)); }
-__device__ __forceinline__ V3 ld3(const float* __restrict__ p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ void st3(float* __restrict__ p, V3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+using namespace gol_vec3;
 
 // gradient of x / max(|x|, eps) for upstream g
 __device__ __forceinline__ V3 normalize_bwd(V3 x, V3 g, float eps) {

@@ -9,6 +9,7 @@
 // the L shadow planes) and the planar outputs once: HBM-bound for small L, VALU-bound at L = 32.
 // Backward recomputes the per-light terms (no saved intermediates).
 #include "gol_common.h"
+#include "gol_vec3.h"
 
 namespace {
 
@@ -16,13 +17,7 @@ constexpr float kPi = 3.14159265358979323846f;
 constexpr float kEps = 1e-12f;  // F.normalize eps
 constexpr float kLn2 = 0.69314718056f;
 
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return V3{a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 ld3(const float* __restrict__ p) { return V3{p[0], p[1], p[2]}; }
+using namespace gol_vec3;
 __device__ __forceinline__ V3 ldplanar(const float* __restrict__ p, size_t hw) { return V3{p[0], p[hw], p[2 * hw]}; }
 __device__ __forceinline__ void stplanar(float* __restrict__ p, size_t hw, V3 v) { p[0] = v.x; p[hw] = v.y; p[2 * hw] = v.z; }
 

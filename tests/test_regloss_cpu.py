@@ -78,9 +78,10 @@ def test_patch_losses_regularizers_rebinds_exactly_the_seven():
 
 
 def test_kind_constants_are_the_headers_enum():
-    from goliath_amd import losses
+    from goliath_amd import losses, optim
 
     assert (losses.BOUND, losses.NEG_SQ, losses.SQ, losses.ABS, losses.ALPHAPRIOR) == (0, 1, 2, 3, 4)
+    assert losses.regloss_chunk_elems() == optim.chunk_elems()   # both entries return csrc/gol_stream.h's one constant
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "goliath_hip.h")).read()
     for name, value in (("BOUND", 0), ("NEG_SQ", 1), ("SQ", 2), ("ABS", 3), ("ALPHAPRIOR", 4)):
         assert f"GOL_REGLOSS_{name} = {value}" in hdr    # the Python constants are the header's enum
