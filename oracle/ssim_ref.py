@@ -17,14 +17,20 @@ def window(channel, size=11, sigma=1.5):
     return g.mm(g.t()).float()[None, None].expand(channel, 1, size, size).contiguous()                # ssim.py:19-23
 
 
-def ssim(img1, img2, mask=None, size=11):
+def ssim_map(img1, img2, size=11):
+    """The per-pixel SSIM map [B,C,H,W] that ssim() averages, in the dtype of img1 (float32 like the reference, or
+    float64 as the yardstick of the parity tests)."""
     C = img1.shape[-3]
     w = window(C, size).to(img1)
     conv = lambda t: F.conv2d(t, w, padding=size // 2, groups=C)
     mu1, mu2 = conv(img1), conv(img2)                                                                 # ssim.py:26-27
     s11, s22, s12 = conv(img1 * img1) - mu1 * mu1, conv(img2 * img2) - mu2 * mu2, conv(img1 * img2) - mu1 * mu2
     C1, C2 = 0.01 ** 2, 0.03 ** 2
-    m = ((2 * mu1 * mu2 + C1) * (2 * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s11 + s22 + C2))    # ssim.py:40
+    return ((2 * mu1 * mu2 + C1) * (2 * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s11 + s22 + C2))  # ssim.py:40
+
+
+def ssim(img1, img2, mask=None, size=11):
+    m = ssim_map(img1, img2, size)
     if mask is None:
         return m.mean()
     mask = mask.expand(-1, m.shape[1], -1, -1)                                                        # ssim.py:43

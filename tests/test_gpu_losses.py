@@ -1,4 +1,6 @@
 """GPU parity: fused masked L1 image loss vs the reference expression (ca_code/loss/__init__.py:411)."""
+import math
+
 import pytest
 import torch
 
@@ -27,6 +29,72 @@ def test_l1_image_matches_torch(shape, mask_c):
     if mask is not None:
         t["image_mask"] = mask
     assert abs(float(losses.rgb_l1(d, t)) - float(ref)) < 1e-6
+
+
+def _l1_case(shape, mask_kind, seed):
+    """pred, target, mask (CPU float32): ~1 % of the pixels of pred equal target (the kink: gradient exactly 0 there)."""
+    B, C, H, W = shape
+    g = torch.Generator().manual_seed(seed)
+    pred, tgt = torch.rand(shape, generator=g), torch.rand(shape, generator=g)
+    same = torch.rand(shape, generator=g) < 0.01
+    pred = torch.where(same, tgt, pred)
+    if mask_kind == "none":
+        mask = None
+    elif mask_kind == "zero":
+        mask = torch.zeros(B, 1, H, W)
+    elif mask_kind == "frac1":
+        mask = (torch.rand(B, 1, H, W, generator=g) > 0.3).float() * torch.rand(B, 1, H, W, generator=g)
+    else:
+        assert mask_kind == "bc"
+        mask = (torch.rand(B, C, H, W, generator=g) > 0.3).float()
+    return pred, tgt, mask, same
+
+
+# gol_l1_blocks caps the grid at 64 workgroups x 1024 elements x 4: a plane of more than 262144 elements takes a second
+# grid-stride trip.  512 x 516 = 264192 (HW % 4 == 0: vector path); 513 x 513 = 263169 (odd: the scalar path in every
+# workgroup, and the second plane starts at an odd element offset).
+L1_CASES = [((1, 1, 512, 516), "none"), ((1, 1, 512, 516), "frac1"), ((1, 2, 513, 513), "none"),
+            ((1, 2, 513, 513), "frac1"), ((1, 2, 513, 513), "zero"), ((2, 3, 33, 17), "bc")]
+
+
+@pytest.mark.parametrize("shape,mask_kind", L1_CASES, ids=[f"{'x'.join(map(str, s))}-{m}" for s, m in L1_CASES])
+def test_l1_image_vs_float64(shape, mask_kind):
+    from goliath_amd import _lib, losses
+
+    HW = shape[2] * shape[3]
+    if HW > 2048:
+        assert HW > _lib.load().gol_l1_blocks(HW) * 4096 and _lib.load().gol_l1_blocks(HW) == 64      # second trip
+    pred, tgt, mask, same = _l1_case(shape, mask_kind, seed=sum(shape) + len(mask_kind))
+    assert 0 < int(same.sum()) and float(same.float().mean()) < 0.02
+
+    def ref(dtype):
+        p = pred.to(dtype).requires_grad_(True)
+        v = 2.5 * ((p - tgt.to(dtype)) * (1.0 if mask is None else mask.to(dtype))).abs().mean()
+        (gr,) = torch.autograd.grad(v, p)
+        return float(v.detach()), gr
+
+    v64, G64 = ref(torch.float64)
+    v32, _ = ref(torch.float32)
+    p = pred.cuda().requires_grad_(True)
+    out = 2.5 * losses.l1_image(p, tgt.cuda(), None if mask is None else mask.cuda())
+    (G,) = torch.autograd.grad(out, p)
+    G, v_hip = G.cpu(), float(out.detach())
+    assert bool(torch.isfinite(G).all()) and math.isfinite(v_hip)
+    # gradient sign * m * g / n: no rounding beyond the multiplies -> within 2 ulp of the float64 result rounded to
+    # float32, the same sign (and zero) pattern
+    want = G64.float()
+    nz = want != 0
+    ulps = (G[nz].view(torch.int32).long() - want[nz].view(torch.int32).long()).abs()
+    d_ref, d_hip = abs(v32 - v64), abs(v_hip - v64)
+    print(f"l1 {shape} {mask_kind}: max ulp {int(ulps.max()) if ulps.numel() else 0} | value: hip {d_hip:.3e} ref "
+          f"{d_ref:.3e} allowed {4 * d_ref + 2.0 ** -23 * abs(v64):.3e} | signs differ at "
+          f"{int((torch.sign(G) != torch.sign(want)).sum())} of {G.numel()}")
+    assert torch.equal(torch.sign(G), torch.sign(want))
+    assert not G[same].any()
+    if mask_kind == "zero":
+        assert not G.any() and v_hip == 0.0 and v64 == 0.0
+    assert ulps.numel() == 0 or int(ulps.max()) <= 2       # measured: 0 without a mask, 1 with fractional weights
+    assert d_hip <= 4 * d_ref + 2.0 ** -23 * abs(v64), (d_hip, d_ref)
 
 
 @pytest.mark.parametrize("mask_c", [0, 1, 3])
