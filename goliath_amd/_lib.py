@@ -29,6 +29,8 @@ _SYMBOLS = [
     "gol_uvgeom_bwd", "gol_lbs_skeleton_fwd", "gol_lbs_skeleton_bwd", "gol_lbs_skin_fwd", "gol_lbs_skin_bwd",
     "gol_optim_chunk_elems", "gol_optim_grad_stats", "gol_optim_finalize", "gol_optim_adam_step",
     "gol_regloss_chunk_elems", "gol_regloss_fwd", "gol_regloss_bwd", "gol_backlit_fwd", "gol_backlit_bwd",
+    "gol_imgloss_chunk_elems", "gol_imgloss_fwd", "gol_imgloss_finalize", "gol_imgloss_bwd", "gol_depth_disc_mask",
+    "gol_mask_erode",
 ]
 
 

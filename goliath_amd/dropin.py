@@ -121,15 +121,18 @@ def patch_light_decorator(decorator_module=None):
 
 
 REGULARIZER_LOSSES = ("bound_primscale", "negcolor", "l2_reg", "list_l1_reg", "backlit_reg", "alphaprior", "mask_l1")
+IMAGE_LOSSES = ("rgb_l2", "psnr", "rgb_l1_focus", "rgb_l1_phys", "pose_shadow_l2")
 
 
-def patch_losses(registry_module=None, regularizers=False):
+def patch_losses(registry_module=None, regularizers=False, images=False):
     """Re-register the image losses of the reference's loss registry (ca_code/loss/registry.py:59-79; rgb_l1 and
     rgb_ssim, ca_code/loss/__init__.py:391-411, 478-494) with the fused HIP versions, so a `ModularLoss` built from the
     unchanged config picks them up.  Call after `import ca_code.loss` and before constructing the loss.
     regularizers=True also re-registers the per-Gaussian regularisers and their kin (REGULARIZER_LOSSES,
     ca_code/loss/__init__.py:450-453, 560-600, 609-622) with the gol_regloss_* / gol_backlit_* operators of
-    goliath_amd.losses; every other entry of the registry stays the reference's."""
+    goliath_amd.losses; images=True also re-registers the L2 / focus image losses (IMAGE_LOSSES,
+    ca_code/loss/__init__.py:366-386, 415-445, 496-538, 555-557) with the gol_imgloss_* operators.  Every other entry of the
+    registry stays the reference's."""
     from . import losses
 
     if registry_module is None:
@@ -144,7 +147,33 @@ def patch_losses(registry_module=None, regularizers=False):
     if regularizers:
         for name in REGULARIZER_LOSSES:
             registry_module.loss_registry[name] = factory(getattr(losses, name))
+    if images:
+        for name in IMAGE_LOSSES:
+            registry_module.loss_registry[name] = factory(getattr(losses, name))
     return registry_module
+
+
+IMAGE_OP_MODULES = ("ca_code.models.urhand", "ca_code.models.mesh_vae", "ca_code.models.mesh_vae_drivable", "ca_code.loss")
+
+
+def patch_image_ops(*modules):
+    """Rebind the module-level names `depth_discontuity_mask` (ca_code/utils/geom.py:768-794, imported at urhand.py:31,
+    mesh_vae.py:31 and mesh_vae_drivable.py:31) and `erode` (ca_code/utils/image.py:411-422, imported at
+    ca_code/loss/__init__.py:31) to goliath_amd.imageops in the modules given (default: IMAGE_OP_MODULES, imported here),
+    wherever a module carries the name; a module without it is left alone.  Returns the list of (module name, attribute) pairs that were rebound."""
+    import importlib
+
+    from . import imageops
+
+    if not modules:
+        modules = tuple(importlib.import_module(name) for name in IMAGE_OP_MODULES)
+    done = []
+    for mod in modules:
+        for attr, fn in (("depth_discontuity_mask", imageops.depth_discontinuity_mask), ("erode", imageops.erode)):
+            if hasattr(mod, attr):
+                setattr(mod, attr, fn)
+                done.append((getattr(mod, "__name__", repr(mod)), attr))
+    return done
 
 
 def patch_urhand(urhand_module=None, mesh_render_layer=False):

@@ -8,6 +8,11 @@ and the per-Gaussian regularisers (csrc/regloss.hip): one read pass forward, one
   backlit(color, cos_weight)     sum(w * relu(color)) / (1 + sum(w)), w = relu(-cos_weight)^2
   bound_primscale, negcolor, l2_reg, list_l1_reg, backlit_reg, alphaprior, mask_l1
                                 <- ca_code/loss/__init__.py:560-600, 609-622, 450-453  (same signatures / keys)
+
+and the masked image penalties (csrc/imgfam.hip): kernel + finalize forward, one kernel backward, the mean on the device
+  image_penalty(pred, target, kind, mask, veto)  mean of |x|, x^2 or |x| exp(|x| / 255) of x = (pred - target) mask (1 - veto)
+  rgb_l2, psnr, rgb_l1_focus, rgb_l1_phys, pose_shadow_l2
+                                <- ca_code/loss/__init__.py:366-386, 415-445, 496-538, 555-557  (same signatures / keys)
 """
 from typing import Optional
 
@@ -260,3 +265,154 @@ def mask_l1(preds, targets, src_key: str = "rendered_mask", tgt_key: str = "imag
     if pred.dim() < 2:
         pred, target = pred.reshape(1, 1, -1), target.reshape(1, 1, -1)
     return l1_image(pred, target.expand_as(pred) if target.shape != pred.shape else target)
+
+
+# ---- masked image penalties (gol_imgloss_*, csrc/imgfam.hip) ----------------------------------------------------------
+IMG_ABS, IMG_SQ, IMG_EXPW = range(3)   # gol_imgloss_kind of include/goliath_hip.h
+
+
+def imgloss_chunk_elems():
+    return _lib.load().gol_imgloss_chunk_elems()
+
+
+def _imgloss_args(kind, pred, target, mask, veto):
+    B, C = pred.shape[:2]
+    HW = pred[0, 0].numel()
+    mask_c = 0 if mask is None else mask.shape[1]
+    return (c_int(kind), c_int(B), c_int(C), c_int(HW), c_int(mask_c), fptr(pred), fptr(target), fptr(mask),
+            ptr(veto, torch.uint8))
+
+
+class _ImagePenalty(torch.autograd.Function):
+    """kernel, finalize forward; kernel backward (plus the one scalar division upstream / n)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask, veto, kind):
+        B, C = pred.shape[:2]
+        HW = pred[0, 0].numel()
+        n = B * C * HW
+        nb = B * C * -(-HW // imgloss_chunk_elems())
+        partial = torch.empty(nb, device=pred.device, dtype=torch.float64)
+        loss = torch.empty((), device=pred.device, dtype=torch.float32)
+        total = torch.empty((), device=pred.device, dtype=torch.float64)
+        with _lib.device_guard(pred.device):
+            _lib.call("gol_imgloss_fwd", *_imgloss_args(kind, pred, target, mask, veto), ptr(partial, torch.float64),
+                      stream_ptr())
+            _lib.call("gol_imgloss_finalize", c_i64(nb), c_i64(n), ptr(partial, torch.float64), fptr(loss),
+                      ptr(total, torch.float64), stream_ptr())
+        ctx.save_for_backward(pred, target, mask, veto)
+        ctx.kind = kind
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        pred, target, mask, veto = ctx.saved_tensors
+        out = torch.empty_like(pred)
+        gs = (g.to(torch.float32) / pred.numel()).reshape(1).contiguous()
+        with _lib.device_guard(pred.device):
+            _lib.call("gol_imgloss_bwd", *_imgloss_args(ctx.kind, pred, target, mask, veto), fptr(gs), fptr(out),
+                      stream_ptr())
+        return out, None, None, None, None
+
+
+def image_penalty(pred: torch.Tensor, target: torch.Tensor, kind: int, mask: Optional[torch.Tensor] = None,
+                  veto: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mean(f((pred - target) * mask * (1 - veto))) over [B,C,...] images for the penalty `kind` (IMG_ABS |x|, IMG_SQ x^2,
+    IMG_EXPW |x| exp(|x| / 255) with the weight detached; f and its gradient as listed at gol_imgloss_fwd in
+    include/goliath_hip.h).  mask: float [B,1,...] or [B,C,...] or None; veto: torch.bool (or uint8) [B,1,...] or None, read
+    as bytes without a conversion pass.  A float32 scalar, differentiable in pred only."""
+    if not (pred.is_cuda and target.is_cuda):
+        raise _lib.GoliathHipError("image_penalty needs CUDA(HIP) tensors; there is no CPU path")
+    if pred.dim() < 3 or pred.numel() == 0:
+        raise ValueError(f"image_penalty: pred {tuple(pred.shape)} is not a non-empty [B,C,...] image")
+    if target.shape != pred.shape:
+        target = target.expand_as(pred)
+    planes = lambda t: t.shape[0] == pred.shape[0] and t.shape[2:] == pred.shape[2:]
+    if mask is not None and not (mask.dim() == pred.dim() and planes(mask) and mask.shape[1] in (1, pred.shape[1])):
+        raise ValueError(f"image_penalty: mask {tuple(mask.shape)} does not fit pred {tuple(pred.shape)}")
+    if veto is not None:
+        if veto.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("image_penalty: veto must be torch.bool or torch.uint8 (fold a float one into the mask)")
+        if not (veto.dim() == pred.dim() and planes(veto) and veto.shape[1] == 1):
+            raise ValueError(f"image_penalty: veto {tuple(veto.shape)} does not fit pred {tuple(pred.shape)}")
+        veto = veto.detach().contiguous()
+        veto = veto.view(torch.uint8) if veto.dtype == torch.bool else veto
+    c = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
+    return _ImagePenalty.apply(pred.to(torch.float32).contiguous(), c(target), c(mask), veto, int(kind))
+
+
+def _hip_erode(mask: torch.Tensor, ks: int) -> torch.Tensor:
+    from . import imageops
+
+    return imageops.erode_planes(mask, ks)
+
+
+def _image_mask(mask, ddisc, mask_erode):
+    """The mask product of the reference's image losses (ca_code/loss/__init__.py:376-385, 498-507) as (mask, veto): the
+    erosion on gol_mask_erode, a boolean depth_disc_mask handed on as the kernel's veto, a float one folded into the mask in
+    torch (`mask * (1 - ddisc)`, the reference's `try` branch)."""
+    if mask_erode is not None:
+        mask = _hip_erode(mask, mask_erode)      # erode(mask.to(th.float32), ks).to(th.bool), kept as float 0 / 1
+    veto = None
+    if ddisc is not None:
+        if ddisc.dtype == torch.bool:
+            veto = ddisc
+        else:
+            mask = (1 - ddisc) if mask is None else mask * (1 - ddisc)
+    if veto is not None and (veto.dim() < 3 or veto.shape[1] != 1):   # not one flag per pixel: fold it in torch
+        mask, veto = ((~veto).to(torch.float32) if mask is None else mask * ~veto), None
+    return (None if mask is None else mask.to(torch.float32)), veto
+
+
+def _masked_penalty(kind, pred, target, mask, ddisc, mask_erode):
+    if not (pred.is_cuda and target.is_cuda):
+        raise _lib.GoliathHipError("the fused image losses need CUDA(HIP) tensors; there is no CPU path")
+    mask, veto = _image_mask(mask, ddisc, mask_erode)
+    return image_penalty(pred, target, kind, mask, veto)
+
+
+def rgb_l2(preds, targets, src_key: str = "rendered_rgb", tgt_key: str = "image", mask_key: str = "image_mask",
+           ddisc_key: str = "depth_disc_mask", mask_erode: Optional[int] = None):
+    """Same semantics as the reference's rgb_l2 (ca_code/loss/__init__.py:366-386); an absent mask costs no pass (with
+    `mask_erode` it is a mask of ones, one channel)."""
+    mask = targets.get(mask_key, preds.get(mask_key, None))
+    if mask is None and mask_erode is not None:
+        mask = torch.ones_like(preds[src_key][:, :1])
+    return _masked_penalty(IMG_SQ, preds[src_key], targets[tgt_key], mask, preds.get(ddisc_key, None), mask_erode)
+
+
+def psnr(preds, targets, src_key: str = "rendered_rgb", tgt_key: str = "image", mask_key: str = "image_mask",
+         data_range: float = 1., ddisc_key: str = "depth_disc_mask", mask_erode: Optional[int] = None):
+    """Same semantics as the reference's psnr (ca_code/loss/__init__.py:415-445): formed from the fused mean squared error
+    on the device in float32; the two constants are float32 logarithms taken on the host, so nothing is copied or synced."""
+    msqerr = rgb_l2(preds, targets, src_key, tgt_key, mask_key, ddisc_key, mask_erode)
+    two_log_range = float(2 * torch.log(torch.tensor(data_range, dtype=torch.float32)))
+    scale = float(10 / torch.log(torch.tensor(10.)))
+    return (two_log_range - torch.log(msqerr)) * scale
+
+
+def _focus(preds, targets, pred_key, mask_erode, self_mask):
+    mask = preds['rendered_mask'].detach() if self_mask else targets['image_mask']
+    return _masked_penalty(IMG_EXPW, preds[pred_key], targets["image"], mask, preds['depth_disc_mask'], mask_erode)
+
+
+def rgb_l1_focus(preds, targets, mask_erode=None, img_blur=False, self_mask=False):
+    """Same semantics as the reference's rgb_l1_focus (ca_code/loss/__init__.py:496-517)."""
+    return _focus(preds, targets, "rendered_rgb_blur" if img_blur else "rendered_rgb", mask_erode, self_mask)
+
+
+def rgb_l1_phys(preds, targets, mask_erode=None, img_blur=False, self_mask=False):
+    """Same semantics as the reference's rgb_l1_phys (ca_code/loss/__init__.py:519-538; `img_blur` is unused there too)."""
+    return _focus(preds, targets, "rendered_phys_rgb", mask_erode, self_mask)
+
+
+def pose_shadow_l2(preds, batch=None):
+    """Same semantics as the reference's pose_shadow_l2 (ca_code/loss/__init__.py:555-557): the target is detached."""
+    pred, target = preds["pose_shadow_map"], preds["shadow_map"]
+    if not (pred.is_cuda and target.is_cuda):
+        raise _lib.GoliathHipError("pose_shadow_l2 needs CUDA(HIP) tensors; there is no CPU path")
+    if pred.dim() < 3:
+        pred, target = pred.reshape(1, 1, -1), target.expand_as(pred).reshape(1, 1, -1)
+    return image_penalty(pred, target, IMG_SQ)

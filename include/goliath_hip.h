@@ -796,6 +796,52 @@ int gol_backlit_fwd(int64_t m, int c, const float* color, const float* cosw, dou
 int gol_backlit_bwd(int64_t m, int c, const float* color, const float* cosw, const float* g_scale, float* g_color,
                     void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * imgfam: the image-sized work around the L2 / focus image losses (csrc/imgfam.hip).  Each entry replaces a chain of ATen
+ * launches over full images by one read pass (and, where something is produced, one write pass).
+ * gol_imgloss_fwd / _bwd / _finalize: a masked elementwise penalty over pred, target [B,C,HW] (float32).
+ *   residual x = (pred - target) * m, m = mask * (1 - veto): mask float32 [B,1,HW] (mask_c = 1) or [B,C,HW] (mask_c = C) or
+ *   NULL (factor 1, mask_c unread); veto bytes [B,1,HW] or NULL (factor 1) -- the storage of a torch.bool depth_disc_mask,
+ *   a non-zero byte vetoes the pixel.  With a = |x| and g = g_scale[0]:
+ *   kind               loss per element     gradient w.r.t. pred                  replaces ca_code/loss/__init__.py
+ *   GOL_IMGLOSS_ABS    a                    sign(x) m g, 0 at 0                   :391-411 rgb_l1's chain
+ *   GOL_IMGLOSS_SQ     x x                  (g (2 x)) m                           :366-386 rgb_l2, :415-445 psnr,
+ *                                                                                 :555-557 pose_shadow_l2
+ *   GOL_IMGLOSS_EXPW   a expf(a / 255.f)    (g expf(a / 255.f)) sign(x) m         :496-517 rgb_l1_focus, :519-538 rgb_l1_phys
+ *                                           (the weight is detached there: it has no derivative)
+ *   A CHUNK is gol_imgloss_chunk_elems() consecutive floats of one (b,c) plane, one workgroup each: 16-byte accesses on full
+ *   chunks of 16-byte aligned planes, scalar ones with the same elements per lane otherwise (the same bits either way).
+ *   fwd: partial[B*C * cdiv(HW, chunk)] (double) = the chunk sums, plane-major.
+ *   finalize: one workgroup adds partial[0 .. n_chunks) in a fixed order in double: loss[0] = (float)(sum / n), sum[0] = sum.
+ *   bwd: g_pred[B,C,HW] written in full; g_scale is a DEVICE scalar (upstream gradient / n).
+ *   float32 arithmetic in torch's operation order without contraction, IEEE division, accurate expf; only finite inputs are
+ *   specified.  B*C <= 65535.  An unknown kind, a mask_c that is neither 1 nor C, or a null pointer with positive sizes
+ *   returns GOL_ERR_INVALID_ARG; B == 0 or HW == 0 returns GOL_OK without a launch.
+ * gol_depth_disc_mask: ca_code/utils/geom.py:768-794 depth_discontuity_mask.  depth [B,H,W] float32 -> out [B,H,W] bytes
+ *   (0 / 1): the two 3x3 Sobel kernels with zero padding, a centre fires when sqrtf(gx gx + gy gy) > threshold, and an
+ *   output pixel is set when any in-image centre of its pool x pool window fires (avg_pool2d with zero padding > 0).
+ *   pool 1, 3 or 5 (the reference's default is 3), else GOL_ERR_UNSUPPORTED.  (The reference's kscale is unused there.)
+ * gol_mask_erode: ca_code/utils/image.py:393-422 erode.  x [B,H,W], float32 (x_is_u8 = 0) or bytes (x_is_u8 = 1: the
+ *   storage of a torch.bool) -> out [B,H,W] float32 0 / 1: 1 iff no in-image pixel of the ks x ks window has 1 - x > 0
+ *   (bytes: is 0); pixels outside the image do not veto (the zero-padded complement).  DEFINED FOR x IN [0,1]: the
+ *   reference sums 1 - x over the window, which a value above 1 could cancel.  ks odd in 1 .. 31, else GOL_ERR_UNSUPPORTED.
+ * Both mask operators: one workgroup per 64 x 16 output tile, tile + halo staged in LDS; B <= 65535.
+ * Fixed-order sums in double, no atomics: bitwise reproducible.  No host sync, no allocation: captures as a linear graph.
+ * ---------------------------------------------------------------------------------------- */
+typedef enum {
+  GOL_IMGLOSS_ABS = 0,
+  GOL_IMGLOSS_SQ = 1,
+  GOL_IMGLOSS_EXPW = 2
+} gol_imgloss_kind;
+int gol_imgloss_chunk_elems(void);
+int gol_imgloss_fwd(int kind, int B, int C, int HW, int mask_c, const float* pred, const float* target, const float* mask,
+                    const uint8_t* veto, double* partial, void* stream);
+int gol_imgloss_finalize(int64_t n_chunks, int64_t n, const double* partial, float* loss, double* sum, void* stream);
+int gol_imgloss_bwd(int kind, int B, int C, int HW, int mask_c, const float* pred, const float* target, const float* mask,
+                    const uint8_t* veto, const float* g_scale, float* g_pred, void* stream);
+int gol_depth_disc_mask(int B, int H, int W, int pool, float threshold, const float* depth, uint8_t* out, void* stream);
+int gol_mask_erode(int B, int H, int W, int ks, int x_is_u8, const void* x, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
