@@ -359,6 +359,10 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
     return (tid < kBatchB && e >= range.x) ? ids[e] : 0;
   };
   int gid_next = entry_id(0);
+  // (PACKED) bytes of a gradient record as a value the compiler cannot see through: with the constant, id * 64 + base
+  // becomes a 64-bit shift and a 64-bit add per atomic; with an opaque factor it is one v_mad_u64_u32
+  unsigned rec_bytes = GOL_GRAD_RECORD * sizeof(float);
+  if (PACKED) asm volatile("" : "+s"(rec_bytes));
   for (int bb = 0; bb < n_batches; ++bb) {
     __syncthreads();
     const int batch_end = bmax - bb * kBatchB;
@@ -431,31 +435,75 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
     if (PACKED) {
       // gradients live in 64-byte records [r g b | opacity | x y | conic a b c | extra | pad]: 16 consecutive
       // lanes own one Gaussian's record, so an atomic instruction touches 4 cache lines instead of 64
-      float* rec = v_colors;
-      for (int idx = tid; idx < batch_size * 16; idx += NT) {
-        const int t = idx >> 4, c = idx & 15;
+      // The merge of a batch: two phases with a barrier between them.
+      // Phase 1, one thread per entry (wave 0; an entry past batch_size has no flag set): the waves' slot rows are summed
+      // and the entry's weights formed ONCE -- not once per (entry, component) lane, which cost ~590 VALU per full batch
+      // against ~70 now -- and the finished record goes back into wave 0's row in record order.  Each thread reads all
+      // rows of its own entry before it writes one of them.
+      if (tid < kBatchB) {
+        int tw[NW];   // the flags of all waves in flight together
+#pragma unroll
+        for (int w = 0; w < NW; ++w) tw[w] = s_touched[w][tid];
+        float s[kAcc];
+#pragma unroll
+        for (int k = 0; k < kAcc; ++k) s[k] = 0.f;
         bool any = false;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) any = any || (s_touched[w][t] != 0);
-        if (!any || c > (EXTRA ? 9 : 8)) continue;
-        // (the three merges keep their own arithmetic form of the weights: a common one changes these kernels' code)
-        // component c = w1 * S[k1] + w2 * S[k2] of the wave-summed slots S; slots 4..8 hold moments of gop:
-        // v_sigma-sums = -opacity * moment (conic back from its log2e scaling with ln 2)
-        const float4 a4 = s_e[t].a;
-        const float4 b4 = s_e[t].b;
-        const float nop = -b4.y, cc = b4.x;
-        const int k1 = (c == 5) ? 4 : c, k2 = 5;
-        const float w1 = (c == 4) ? nop * a4.z * kUnA : (c == 5) ? nop * a4.w * kUnB : (c == 6 || c == 8) ? 0.5f * nop
-                       : (c == 7) ? nop : 1.f;
-        const float w2 = (c == 4) ? nop * a4.w * kUnB : (c == 5) ? nop * cc * kUnA : 0.f;
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
         for (int w = 0; w < NW; ++w) {
-          const bool tw = s_touched[w][t] != 0;
-          s1 += tw ? s_acc[w][t][k1] : 0.f;
-          s2 += tw ? s_acc[w][t][k2] : 0.f;
+          if (tw[w]) {
+            any = true;
+            const float4* q = reinterpret_cast<const float4*>(&s_acc[w][tid][0]);
+            const float4 q0 = q[0], q1 = q[1], q2 = q[2];
+            s[0] += q0.x; s[1] += q0.y; s[2] += q0.z; s[3] += q0.w;
+            s[4] += q1.x; s[5] += q1.y; s[6] += q1.z; s[7] += q1.w;
+            s[8] += q2.x; s[9] += q2.y;
+          }
         }
-        atomicAdd(rec + (goff + (size_t)s_id[t]) * 16 + c, w1 * s1 + w2 * s2);
+        if (any) {
+          // (the three merges keep their own arithmetic form of the weights: a common one changes these kernels' code)
+          // slots 4..8 hold moments of gop: v_sigma-sums = -opacity * moment (conic back from its log2e scaling with ln 2)
+          const float4 a4 = s_e[tid].a;
+          const float4 b4 = s_e[tid].b;
+          const float nop = -b4.y, cc = b4.x;
+          const float wxx = nop * a4.z * kUnA, wxy = nop * a4.w * kUnB, wyy = nop * cc * kUnA, hnop = 0.5f * nop;
+          float4* o = reinterpret_cast<float4*>(&s_acc[0][tid][0]);
+          o[0] = make_float4(s[0], s[1], s[2], s[3]);
+          o[1] = make_float4(wxx * s[4] + wxy * s[5], wxy * s[4] + wyy * s[5], hnop * s[6], nop * s[7]);
+          *reinterpret_cast<float2*>(o + 2) = make_float2(hnop * s[8], s[9]);
+          s_touched[0][tid] = 1;
+        }
+      }
+      __syncthreads();
+      // Phase 2: lane (t, c) adds component c of entry t's record; the lane's component, and with it the address part that
+      // does not depend on the entry, stays the same over the loop (NT is a multiple of 16)
+      const int c = tid & 15;
+      if (c <= (EXTRA ? 9 : 8)) {
+        float* rec_c = v_colors + goff * 16 + c;
+        // A fixed trip count (entries past batch_size have no flag set) in chunks of four entries per lane whose LDS reads
+        // are in flight together.  One entry per iteration (flag, then id and value: two dependent LDS round trips each)
+        // makes the merge a latency chain per batch; 8 views per launch hide it behind other waves, the shorter launches
+        // of the two-stream step and of single views do not (step 2.67 -> 2.66 ms with that loop, 2.61 ms with this one).
+        // Whole batches in flight (kCh = kIt, phase 1 alike) gain another 0.2 % but cost the 4-wave kernel two waves per SIMD.
+        constexpr int kIt = kBatchB * 16 / NT, kCh = 4;
+        static_assert(kIt % kCh == 0, "the merge issues its atomics in chunks of kCh entries per lane");
+#pragma unroll
+        for (int i0 = 0; i0 < kIt; i0 += kCh) {
+          int flag[kCh], id[kCh];
+          float val[kCh];
+#pragma unroll
+          for (int i = 0; i < kCh; ++i) {
+            const int t = (tid >> 4) + (i0 + i) * (NT / 16);
+            flag[i] = s_touched[0][t]; id[i] = s_id[t]; val[i] = s_acc[0][t][c];
+          }
+#pragma unroll
+          for (int i = 0; i < kCh; ++i) {
+            // record of the entry: id x rec_bytes + rec_c as ONE v_mad_u64_u32 (see rec_bytes)
+            if (flag[i]) {
+              char* r = reinterpret_cast<char*>(rec_c) + (uint64_t)(unsigned)id[i] * rec_bytes;
+              atomicAdd(reinterpret_cast<float*>(r), val[i]);
+            }
+          }
+        }
       }
     } else if (tid < batch_size) {
       float a[kAcc];
