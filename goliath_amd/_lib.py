@@ -30,7 +30,7 @@ _SYMBOLS = [
     "gol_optim_chunk_elems", "gol_optim_grad_stats", "gol_optim_finalize", "gol_optim_adam_step",
     "gol_regloss_chunk_elems", "gol_regloss_fwd", "gol_regloss_bwd", "gol_backlit_fwd", "gol_backlit_bwd",
     "gol_imgloss_chunk_elems", "gol_imgloss_fwd", "gol_imgloss_finalize", "gol_imgloss_bwd", "gol_depth_disc_mask",
-    "gol_mask_erode",
+    "gol_mask_erode", "gol_envbg_blur_taps", "gol_envbg_scratch_floats", "gol_envbg_image", "gol_envbg_compose",
 ]
 
 

@@ -6,6 +6,7 @@
     dropin.patch_light_decorator()  # optional: the env-relight driver hands over ONE shared pyramid (config 2)
     dropin.patch_geometry()       # optional: GeometryModule.to_uv / .vn and the decoder's postex / tn on the uvgeom kernels
     dropin.patch_lbs()            # optional: LinearBlendSkinning / LBSModule.pose on the fused skeleton + skinning kernels
+    dropin.patch_relight_vis()    # optional, with patch_rgca(): run_vis_relight's frames from ONE render + the HIP env background
 
 `install()` registers the module names the reference imports for its native code:
     gsplat            project_gaussians, rasterize_gaussians   (ca_code/utils/render_gsplat.py:10-11)
@@ -48,6 +49,22 @@ def patch_rgca(rgca_module=None):
     rgca_module.AutoEncoder.render = fused.autoencoder_render
     rgca_module.AutoEncoder.forward = fused.autoencoder_forward
     rgca_module.PrimDecoder.forward = fused.prim_decoder_forward
+    return rgca_module
+
+
+def patch_relight_vis(rgca_module=None):
+    """Opt in to the fused relight visualisation: with it (and patch_rgca(), which installs the forward that reads the flag)
+    the `envbg` branch of AutoEncoder.forward (rgca.py:232-245, what run_vis_relight.py:110-122 calls under no_grad) makes
+    ONE render -- the diffuse / specular breakdown rides as six extra channels over the lit render's tile lists
+    (gol_rasterize_nd_fwd) instead of two further project + bin + sort + raster passes -- and composites the env-map
+    background and the mirror ball with goliath_amd.envbg (gol_envbg_image / gol_envbg_compose) instead of
+    ca_code.utils.envmap.compose_envmap's bicubic grid_sample + 101 x 101 depthwise conv2d.  Forward-only: with grad mode
+    on the branch stays the reference's.  Sets a class flag on AutoEncoder; idempotent.  Returns the patched module."""
+    from . import rgca as fused
+
+    if rgca_module is None:
+        import ca_code.models.rgca as rgca_module
+    setattr(rgca_module.AutoEncoder, fused.RELIGHT_VIS_FLAG, True)
     return rgca_module
 
 

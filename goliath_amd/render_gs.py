@@ -40,23 +40,30 @@ def render(cam_img_w: int, cam_img_h: int, fx: float, fy: float, cx: float, cy: 
 
 
 def render_batch(K: th.Tensor, Rt: th.Tensor, preds: Dict[str, Any], height: int, width: int,
-                 l1_target: Optional[th.Tensor] = None, l1_mask: Optional[th.Tensor] = None):
+                 l1_target: Optional[th.Tensor] = None, l1_mask: Optional[th.Tensor] = None,
+                 extra_colors: Optional[th.Tensor] = None):
     """AutoEncoder.render semantics (rgca.py:112-151): rgb[B,3,H,W], alpha = 1 - T.detach(),
     depth / alpha.clamp(0.05, 1).  K[B,3,3] and Rt[B,3,4] stay on the device.
     With l1_target (and optionally l1_mask) a fourth value is returned: the masked L1 loss of rgb against it
-    (rgb_l1, ca_code/loss/__init__.py:391-411), fused into the raster passes."""
+    (rgb_l1, ca_code/loss/__init__.py:391-411), fused into the raster passes.
+    With extra_colors[B,N,Ce] (forward-only) a last value is returned: those channels composited over the same tile lists,
+    [B,Ce,H,W] (splat.render_views(extra_colors=...))."""
     pr = preds.get("projected")
     if pr is not None and pr.valid_for(preds, K, Rt, height, width) and (pr.views.glob_scale, pr.views.clip_thresh) == (1.0, 0.1):
         # the shading kernel already projected these Gaussians onto these cameras (shading_tail(..., views=...)): start at
         # the tile count; the backward hands its gradient records to the shading backward
         out = render_views(None, None, None, None, None, None, None, height, width, with_depth=True, l1_target=l1_target,
-                           l1_mask=l1_mask, raw_depth=False, projected=pr)
+                           l1_mask=l1_mask, raw_depth=False, projected=pr, extra_colors=extra_colors)
     else:
         intr = th.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], dim=-1)
         out = render_views(preds["primpos"], preds["primscale"], preds["primqvec"], preds["opacity"],
                            preds["color"], Rt, intr, height, width, with_depth=True, l1_target=l1_target, l1_mask=l1_mask,
-                           raw_depth=False)  # only depth / alpha.clamp(0.05, 1) leaves AutoEncoder.render
+                           raw_depth=False,  # only depth / alpha.clamp(0.05, 1) leaves AutoEncoder.render
+                           extra_colors=extra_colors)
     # alpha = 1 - T.detach() and depth / alpha.clamp(0.05, 1) are written by the raster kernel's epilogue
+    ret = (out["render"], out["alpha"].detach(), out["depth_norm"])
     if l1_target is not None:
-        return out["render"], out["alpha"].detach(), out["depth_norm"], out["l1_loss"]
-    return out["render"], out["alpha"].detach(), out["depth_norm"]
+        ret += (out["l1_loss"],)
+    if extra_colors is not None:
+        ret += (out["extra"],)
+    return ret

@@ -21,6 +21,9 @@ from .uvgeom import fused_topology, uv_geometry
 from .views import ViewSet
 
 
+RELIGHT_VIS_FLAG = "_goliath_relight_vis"   # class attribute of AutoEncoder set by dropin.patch_relight_vis()
+
+
 def _fuse_projection() -> bool:
     """GOLIATH_FUSED_PROJECTION=0: shade and project as separate kernels (rounds 1-3)."""
     return os.environ.get("GOLIATH_FUSED_PROJECTION", "1") != "0"
@@ -79,9 +82,30 @@ def autoencoder_forward(
     finally:
         self.decoder._goliath_view_set = None
     preds = {"geom": geom, "headrel_light_sh": headrel_light_sh, **enc_preds, **dec_preds}
+    vis = preconv_envmap is not None and "envbg" in kwargs
+    if vis and getattr(self, RELIGHT_VIS_FLAG, False) and not th.is_grad_enabled():
+        # dropin.patch_relight_vis(): the visualisation branch below with ONE projection / binning / list walk -- the
+        # diffuse and specular breakdown (rgca.py:239-243) rides as six extra channels over the lit render's own tile lists
+        # -- and the env-map background and mirror ball on the HIP kernels of goliath_amd.envbg (no ca_code.utils.envmap)
+        from .envbg import compose_envmap
+
+        parts = th.cat([preds["diff_color"].clamp(min=0.0), preds["spec_color"].clamp(min=0.0)], dim=-1)
+        rgb, alpha, depth, parts = self.render(K, headrel_Rt, dict(preds, extra_colors=parts))
+        preds.pop("projected", None)
+        rgb, _ = autoencoder_image_tail(_NoBlur(self), rgb, alpha, camera_id, background, is_fully_lit_frame)
+        envbg = kwargs["envbg"]
+        if envbg.shape[0] != rgb.shape[0]:
+            envbg = envbg.expand(rgb.shape[0], -1, -1, -1)
+        rgb = th.cat([compose_envmap(rgb, alpha, envbg, K, Rt), parts[:, :3], parts[:, 3:]], -1)
+        preds["color"] = preds["spec_color"].clamp(min=0.0)   # (what the reference's last breakdown render leaves behind)
+        preds.update(rgb=rgb, alpha=alpha, depth=depth)
+        if getattr(self, "learn_blur_enabled", False):
+            preds["rgb"] = autoencoder_image_tail(_OnlyBlur(self), rgb, alpha, camera_id)[0]
+            preds["learn_blur_weights"] = self.learn_blur.reg(camera_id)
+        return preds
     rgb, alpha, depth = self.render(K, headrel_Rt, preds)
     preds.pop("projected", None)   # (consumed by the render; the returned dict has the reference's keys)
-    if preconv_envmap is not None and "envbg" in kwargs:
+    if vis:
         # visualisation-only branch (run_vis_relight.py): calibrate / composite like the reference, then the env-map
         # background and the diffuse / specular breakdown renders (rgca.py:232-245) with the reference's own helper
         from ca_code.utils.envmap import compose_envmap
@@ -127,8 +151,10 @@ def _OnlyBlur(model):
 
 
 def autoencoder_render(self, K: th.Tensor, Rt: th.Tensor, preds: Dict[str, Any]):
-    """All B views in one launch sequence; K stays on the device (no .item())."""
-    return render_batch(K, Rt, preds, self.height, self.width)
+    """All B views in one launch sequence; K stays on the device (no .item()).  A `preds["extra_colors"]`[B,N,Ce] (forward-
+    only; the reference's signature has no room for it, and its decoder returns no such key) adds a fourth value: those
+    channels composited over the same tile lists, [B,Ce,H,W]."""
+    return render_batch(K, Rt, preds, self.height, self.width, extra_colors=preds.get("extra_colors"))
 
 
 def random_light_sh(sh_fn, n_diff_sh: int, batch: int, device, dtype):

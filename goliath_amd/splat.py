@@ -734,7 +734,7 @@ def raster_pair_counts(res):
 
 def render_views(means, scales, quats, opacity, colors, viewmats, intrins, img_h, img_w,
                  background=None, glob_scale=1.0, clip_thresh=0.1, with_depth=True, capacity=None, depth_norm_lo=0.05,
-                 l1_target=None, l1_mask=None, raw_depth=True, projected=None):
+                 l1_target=None, l1_mask=None, raw_depth=True, projected=None, extra_colors=None):
     """Render B views in one launch sequence.
 
     means[B,N,3] scales[B,N,3] quats[B,N,4] opacity[B,N] or [B,N,1] colors[B,N,3]  (fp32, GPU)
@@ -751,7 +751,22 @@ def render_views(means, scales, quats, opacity, colors, viewmats, intrins, img_h
     writes one image less; "depth" is then absent from the result.
     projected (a views.Projected out of shading_tail(..., views=...)): the Gaussians are already projected onto these
     cameras by the shading kernel; means ... intrins are ignored (pass None), glob_scale / clip_thresh are the ViewSet's.
+    extra_colors[B,N,Ce] (forward-only: with grad mode on and an input that requires grad this raises): Ce further
+    channels composited over the SAME tile lists and records -- one gol_rasterize_nd_fwd call after the forward has settled
+    its lists (the planner's overflow repair included), black background -- returned as "extra"[B,Ce,H,W].  What the
+    relight visualisation's diffuse / specular breakdown needs (rgca.py:239-243) without projecting, binning and sorting
+    the same Gaussians again.
     """
+    if extra_colors is not None:
+        BN = tuple((projected.records if projected is not None else means).shape[:2])
+        if extra_colors.dim() != 3 or tuple(extra_colors.shape[:2]) != BN or extra_colors.shape[2] < 1:
+            raise ValueError("extra_colors must be [B,N,Ce]")
+        ins = (means, scales, quats, opacity, colors, extra_colors) + (() if projected is None else (projected.records,))
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ins):
+            raise _lib.GoliathHipError("render_views(extra_colors=...) is forward-only: call it under torch.no_grad() or "
+                                       "with detached inputs")
+        if not extra_colors.is_cuda:
+            raise _lib.GoliathHipError("render_views needs CUDA(HIP) tensors; there is no CPU path")
     if projected is not None:
         B, N = projected.records.shape[:2]
         dev = projected.records.device
@@ -821,4 +836,29 @@ def render_views(means, scales, quats, opacity, colors, viewmats, intrins, img_h
         res["depth_norm"] = depth_norm[:, None]  # depth / clamp(alpha.detach(), depth_norm_lo, 1)
     if l1 is not None:
         res["l1_loss"] = l1
+    if extra_colors is not None:
+        res["extra"] = _raster_extra(res, extra_colors)
     return res
+
+
+def _raster_extra(res, extra_colors):
+    """extra_colors[B,N,Ce] composited by the N-channel rasterizer over the tile lists and geometry records the render_views
+    result `res` was rasterized with (its own final_T / final_idx go to buffers of their own: the result's stay as they
+    are); [B,Ce,H,W].  Shape and device of extra_colors were checked at the top of render_views."""
+    B, N, H, W, _ = res._dims
+    ws, L = res._ws, res._L
+    extra_colors = _f32c(extra_colors.detach())
+    Ce = extra_colors.shape[2]
+    dev = ws.device
+    out = torch.empty(B, H, W, Ce, dtype=torch.float32, device=dev)
+    if B == 0 or N == 0:
+        return out.zero_().permute(0, 3, 1, 2).contiguous()
+    final_Ts = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    final_idx = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    a = ws.data_ptr()
+    with _lib.device_guard(dev):
+        _abi_rasterize_nd_fwd(B=B, N=N, C=Ce, img_h=H, img_w=W, tile_bins=a + L.tile_bins, sorted_ids=a + L.sorted_ids,
+                              capacity=res._cap, records=res._src.records, colors=extra_colors,
+                              background=torch.zeros(Ce, dtype=torch.float32, device=dev), out_img=out, final_Ts=final_Ts,
+                              final_idx=final_idx)
+    return out.permute(0, 3, 1, 2).contiguous()

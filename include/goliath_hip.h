@@ -842,6 +842,35 @@ int gol_imgloss_bwd(int kind, int B, int C, int HW, int mask_c, const float* pre
 int gol_depth_disc_mask(int B, int H, int W, int pool, float threshold, const float* depth, uint8_t* out, void* stream);
 int gol_mask_erode(int B, int H, int W, int ks, int x_is_u8, const void* x, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Environment background of the relight visualisation, forward only (csrc/envbg.hip).  Replaces
+ * ca_code/utils/envmap.py:325-345 compose_envmap with what it calls, as run_vis_relight.py:110-122 reaches it through
+ * ca_code/models/rgca.py:232-245.  envbg[B,3,He,We] is the equirectangular map, K[B,3,3] the intrinsics, R[B,3,3] the
+ * camera rotation Rt[:, :3, :3]; all images are planar [B,3,H,W] float32.
+ * gol_envbg_image: envmap.py:169-227 envmap_to_image for D = None.  Per pixel d = ((x - K02) / (K00 focal_scale),
+ *   (y - K12) / (K11 focal_scale), 1), d' = R^T d (out_y = sum_x R[x][y] d[x]) normalised with F.normalize's eps 1e-12,
+ *   u = atan2(d'x, d'z) / pi, v = 2 acos(d'y) / pi - 1 (evaluated in double; acos' argument clamped to [-1, 1]), then
+ *   grid_sample(mode='bicubic', padding_mode='border', align_corners=True): A = -0.75, ix = (u + 1) / 2 (We - 1) unclipped,
+ *   each of the 4 x 4 tap indices clamped to the map.  blur = 1 (the reference's blurbg=True): the 101 x 101 kernel
+ *   exp(-t_i^2) exp(-t_j^2) / sum, t = linspace(-4, 4, 101), conv2d(padding=50) ZERO padding, applied as a row pass and a
+ *   column pass with the weights of gol_envbg_blur_taps (computed on the host in double, handed to the kernels as 101
+ *   floats); the reference's trailing interpolate(size=(h, w)) is the identity.  blur = 0: one launch, scratch may be NULL;
+ *   blur = 1: three launches, scratch = gol_envbg_scratch_floats(B,H,W) floats (two [B,3,H,W] planes).  bg is not clamped.
+ * gol_envbg_compose: the rest of compose_envmap in one pass: out = render + (1 - alpha) clamp(bg, 0, 1), alpha[B,1,H,W];
+ *   then, in the bottom-right ball x ball pixels (the reference: 200), envmap.py:230-248 envmap_to_mirrorball in place:
+ *   p = linspace(-1, 1, ball) both ways, zsq = px^2 + py^2, inside zsq < 1: nz = -sqrt(1 - zsq), ref = -2 nz (px, py, nz)
+ *   + (0, 0, 1), rotated by R^T, NOT normalised, the same u / v and an unblurred, unclamped bicubic lookup of envbg
+ *   replaces the pixel.  ball = 0: no ball (envbg / R may be NULL).  ball > H or ball > W: GOL_ERR_INVALID_ARG.
+ *   out must not overlap an input.
+ * B * 3 <= 65535, H * W < 2^31.  No host sync, no allocation, no atomics: bitwise reproducible, captures as a linear graph.
+ * ---------------------------------------------------------------------------------------- */
+int gol_envbg_blur_taps(double* taps /* [101] */);
+int64_t gol_envbg_scratch_floats(int B, int H, int W);
+int gol_envbg_image(int B, int H, int W, int He, int We, const float* envbg, const float* K, const float* R,
+                    double focal_scale, int blur, float* scratch, float* bg, void* stream);
+int gol_envbg_compose(int B, int H, int W, int He, int We, const float* render, const float* alpha, const float* bg,
+                      const float* envbg, const float* R, int ball, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
