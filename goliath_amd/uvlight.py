@@ -31,11 +31,21 @@ def _c(t):
     return None if t is None else t.detach().to(torch.float32).contiguous()
 
 
+def _powers(spec_powers):
+    powers = tuple(float(v) for v in spec_powers)
+    if len(powers) > MAX_POW:
+        raise ValueError("at most 4 specular powers")
+    if any(not v >= 1.0 for v in powers):
+        # the reference uses 1, 16, 32.  Below 1 the derivative p s^(p-1) is infinite at s = 0 (half of all texel-light
+        # pairs) in the reference too, and at p = 0 the kernel's exp2(p log2 s) is NaN there where torch.pow gives 1
+        raise ValueError(f"specular powers must be >= 1, got {powers}: s^p has an infinite derivative at s = 0 for p < 1 "
+                         "(and 0^0 is NaN in the kernel, 1 in torch.pow)")
+    return powers
+
+
 def _mk(p_uv, nml, cam_pos, light_pos, light_intensity, shadow_map, powers, fresnel=0.0, roughness=None, tex_mean=None):
     if not p_uv.is_cuda:
         raise _lib.GoliathHipError("uvlight needs CUDA(HIP) tensors; there is no CPU path")
-    if len(powers) > MAX_POW:
-        raise ValueError("at most 4 specular powers")
     B, _, H, W = p_uv.shape
     s = UvLightIn()
     s.B, s.L, s.HW, s.n_pow = B, light_pos.shape[1], H * W, len(powers)
@@ -51,7 +61,7 @@ class _Phong(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p_uv, nml, cam_pos, light_pos, light_intensity, shadow_map, powers):
         B, _, H, W = p_uv.shape
-        args = [_c(t) for t in (p_uv, nml, cam_pos, light_pos, light_intensity.reshape(B, -1), shadow_map)]
+        args = [_c(t) for t in (p_uv, nml, cam_pos, light_pos, light_intensity.reshape(B, light_pos.shape[1]), shadow_map)]
         s = _mk(*args, powers)
         diff = torch.empty(B, 1, H, W, device=p_uv.device)
         spec = torch.empty(B, len(powers), 1, H, W, device=p_uv.device)
@@ -76,7 +86,7 @@ class _Ggx(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p_uv, nml, roughness, tex_mean, cam_pos, light_pos, light_intensity, shadow_map, powers, fresnel):
         B, _, H, W = p_uv.shape
-        args = [_c(t) for t in (p_uv, nml, cam_pos, light_pos, light_intensity.reshape(B, -1), shadow_map)]
+        args = [_c(t) for t in (p_uv, nml, cam_pos, light_pos, light_intensity.reshape(B, light_pos.shape[1]), shadow_map)]
         extra = dict(fresnel=fresnel, roughness=_c(roughness), tex_mean=_c(tex_mean))
         s = _mk(*args, powers, **extra)
         feat = torch.empty(B, 1 + len(powers), H, W, device=p_uv.device)
@@ -102,11 +112,11 @@ class _Ggx(torch.autograd.Function):
 def phong_features(p_uv, nml, cam_pos, light_pos, light_intensity, shadow_map=None, spec_powers=SPEC_POWERS):
     """urhand.py:419-445.  p_uv, nml [B,3,S,S]; cam_pos [B,3]; light_pos [B,L,3]; light_intensity [B,L,1];
     shadow_map [B,L,1,S,S] or None -> (diff_feature_raw [B,1,S,S], spec_feature_raw [B,P,1,S,S])."""
-    return _Phong.apply(p_uv, nml, cam_pos, light_pos, light_intensity, shadow_map, tuple(spec_powers))
+    return _Phong.apply(p_uv, nml, cam_pos, light_pos, light_intensity, shadow_map, _powers(spec_powers))
 
 
 def ggx_features(p_uv, nml, cam_pos, light_pos, light_intensity, roughness, tex_mean, shadow_map=None,
                  fresnel=0.04, spec_powers=SPEC_POWERS):
     """urhand.py:508-567 -> (feat_p [B,1+P,S,S], rgb [B,3,S,S] before the global scale of :567)."""
     return _Ggx.apply(p_uv, nml, roughness, tex_mean, cam_pos, light_pos, light_intensity, shadow_map,
-                      tuple(spec_powers), float(fresnel))
+                      _powers(spec_powers), float(fresnel))

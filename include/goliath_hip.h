@@ -466,6 +466,7 @@ int gol_mvp_shadow_march(int N, int group, int H, int W, int K, const float* ray
  *   p_uv[B,3,HW] nml[B,3,HW] cam_pos[B,3] light_pos[B,L,3] light_intensity[B,L]
  *   shadow_map[B,L,HW] or NULL; GGX only: roughness[B,HW] tex_mean[B,3,HW] (0..255), fresnel
  *   pow[n_pow] = spec_powers (urhand.py:277: 1, 16, 32)
+ *                domain: every pow[k] >= 1 (s^p = exp2(p log2 s) is NaN at p = 0, s = 0)
  * phong: diff[B,HW] = diff_feature_raw, spec[B,n_pow,HW] = spec_feature_raw.
  * ggx:   feat[B,1+n_pow,HW] = feat_p (urhand.py:558), rgb[B,3,HW] = phys_tex before the global
  *        scale of :567.  Backward writes g_* in full (no accumulation); lights, camera and the

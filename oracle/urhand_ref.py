@@ -15,6 +15,14 @@ import torch.nn.functional as F
 SPEC_POWERS = (1, 16, 32)  # urhand.py:277
 
 
+def _pow_stack(x, spec_powers):
+    """x^p capped at 1 for every power, stacked on a new dim 2 (of size 0 for an empty power list, which torch.stack
+    refuses)."""
+    if not len(spec_powers):
+        return x[:, :, None][:, :, :0]
+    return torch.stack([x.pow(v).clamp(max=1.0) for v in spec_powers], 2)
+
+
 def phong_features(p_uv, nml, cam_pos, light_pos, light_intensity, shadow_map=None, spec_powers=SPEC_POWERS):
     """p_uv, nml [B,3,S,S]; cam_pos [B,3]; light_pos [B,L,3]; light_intensity [B,L,1]; shadow_map
     [B,L,1,S,S] or None -> diff_feature_raw [B,1,S,S], spec_feature_raw [B,P,1,S,S]."""
@@ -25,7 +33,7 @@ def phong_features(p_uv, nml, cam_pos, light_pos, light_intensity, shadow_map=No
     ref = view - 2.0 * (view * nml).sum(1, keepdim=True) * nml
     diff = (nml[:, None] * l_uv).sum(2, keepdim=True).clamp(0.0, 1.0)
     spec = (ref[:, None] * l_uv).sum(2, keepdim=True).clamp(min=0.0)
-    spec = torch.stack([spec.pow(v).clamp(max=1.0) for v in spec_powers], 2)
+    spec = _pow_stack(spec, spec_powers)
     sh = shadow_map if shadow_map is not None else torch.ones_like(diff)
     diff_p = (diff * I * sh).sum(1)
     spec_p = (spec * I[:, :, None] * sh[:, :, None]).sum(1)
@@ -58,7 +66,7 @@ def ggx_features(p_uv, nml, cam_pos, light_pos, light_intensity, roughness, tex_
     nom = (4 * math.pi * nom0 * nom0 * nom1[:, None] * nom2).clamp(1e-6, 4 * math.pi)
     specular = frac / nom
     diff_cos = (nml[:, None] * Lv).sum(2, keepdim=True).clamp(0.0, 1.0)
-    spec = torch.stack([specular.pow(v).clamp(max=1.0) for v in spec_powers], 2)
+    spec = _pow_stack(specular, spec_powers)
     sh = shadow_map if shadow_map is not None else torch.ones_like(diff_cos)
     lit = (diff_cos[:, :, None] > 0) * 1.0
     diff_p = (diff_cos * I * sh).sum(1)
@@ -71,17 +79,12 @@ def ggx_features(p_uv, nml, cam_pos, light_pos, light_intensity, roughness, tex_
     return feat_p[:, :, 0], rgb
 
 
-def shadow_pcf(depth, Rt, postex, nml=None, focal=1000.0):
-    """Restatement of the per-texel part of get_shadow_map (/root/reference/ca_code/utils/shadowmap.py:30-96) for a
-    given depth image [B,h,w] (the reference obtains it from its drtk render layer): Rt [B,3,4], postex [B,3,H,W],
-    nml [B,3,H,W] or None -> in_shadow [B,1,H,W].  Pinned by tests/golden/shadow_golden.npz (reference-generated)."""
-    import math
-
-    import torch.nn.functional as F
-
+def _shadow_project(depth, Rt, postex, focal):
+    """The projection of shadow_pcf: normalised centre-tap grid coordinates uv [B,H,W,2] (x, y) and the camera-space
+    depth d1 [B,1,H,W], in the dtype of postex."""
     B, _, H, W = postex.shape
     dh, dw = depth.shape[-2:]
-    K = torch.eye(3)[None].repeat(B, 1, 1)
+    K = torch.eye(3, dtype=postex.dtype)[None].repeat(B, 1, 1)
     K[:, 0, 0] = K[:, 1, 1] = focal
     K[:, 0, 2], K[:, 1, 2] = dw / 2, dh / 2
     p = postex.permute(0, 2, 3, 1).reshape(B, -1, 3)
@@ -92,6 +95,16 @@ def shadow_pcf(depth, Rt, postex, nml=None, focal=1000.0):
     d1 = z.view(B, H, W, 1).permute(0, 3, 1, 2)
     uv[..., 0] = (uv[..., 0] - dw / 2.0 - 0.5) / (dw / 2.0)                   # shadowmap.py:55-56
     uv[..., 1] = (uv[..., 1] - dh / 2.0 - 0.5) / (dh / 2.0)
+    return uv, d1
+
+
+def shadow_pcf(depth, Rt, postex, nml=None, focal=1000.0):
+    """Restatement of the per-texel part of get_shadow_map (/root/reference/ca_code/utils/shadowmap.py:30-96) for a
+    given depth image [B,h,w] (the reference obtains it from its drtk render layer): Rt [B,3,4], postex [B,3,H,W],
+    nml [B,3,H,W] or None -> in_shadow [B,1,H,W], in the dtype of the inputs (float32 or float64).  Pinned by
+    tests/golden/shadow_golden.npz (reference-generated)."""
+    dh, dw = depth.shape[-2:]
+    uv, d1 = _shadow_project(depth, Rt, postex, focal)
     dimg = depth[:, None]
     sigma = 0.3 * ((3 - 1) * 0.5 - 1) + 0.8
     vsum, ssum = 0.0, 0.0
@@ -102,8 +115,8 @@ def shadow_pcf(depth, Rt, postex, nml=None, focal=1000.0):
             g[..., 0] += 2.0 / dw * (x - 1)
             g[..., 1] += 2.0 / dh * (y - 1)
             d = F.grid_sample(dimg, g, mode="nearest", align_corners=False)
-            w = F.grid_sample((dimg > 0.0).float(), g, mode="nearest", align_corners=False)
-            valid = wgt * (w > 1e-4).float()
+            w = F.grid_sample((dimg > 0.0).to(dimg.dtype), g, mode="nearest", align_corners=False)
+            valid = wgt * (w > 1e-4).to(dimg.dtype)
             vsum = vsum + valid
             ssum = ssum + valid * (d1 - d / (w + 1e-8)).clamp(min=0)
     out = ssum / (vsum + 1e-6)
@@ -112,3 +125,14 @@ def shadow_pcf(depth, Rt, postex, nml=None, focal=1000.0):
         bc = torch.sigmoid(10 * (nml * vdir).sum(1, keepdim=True))
         out = bc * out + (1.0 - bc) * 1e3
     return out
+
+
+def shadow_pcf_taps(depth, Rt, postex, focal=1000.0):
+    """Where shadow_pcf samples, evaluated in float64 whatever the input dtype: per light camera and texel the two
+    UNNORMALISED coordinates (ix, iy [B,H,W]) that grid_sample(mode="nearest", align_corners=False) rounds (half to even)
+    for the centre tap -- ((g + 1) * size - 1) / 2 of the same uv as shadow_pcf; the other eight taps add 2 / size to g,
+    i.e. exactly +-1 here -- and the camera-space Z [B,H,W].  A tap reads a texel iff 0 <= round(ix) < w and
+    0 <= round(iy) < h."""
+    dh, dw = depth.shape[-2:]
+    uv, d1 = _shadow_project(depth, Rt.double(), postex.double(), focal)
+    return ((uv[..., 0] + 1) * dw - 1) / 2, ((uv[..., 1] + 1) * dh - 1) / 2, d1[:, 0]

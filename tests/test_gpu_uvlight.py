@@ -81,3 +81,114 @@ def test_uvlight_olat_32_lights_vs_oracle():
     rd, rs = urhand_ref.phong_features(p_uv, nml, cam, lp, li, None)
     od, os_ = uvlight.phong_features(p_uv.cuda(), nml.cuda(), cam.cuda(), lp.cuda(), li.cuda(), None)
     assert rel_l2(od, rd) < TOL and rel_l2(os_, rs) < TOL
+
+
+# ---- edge shapes against the float64 oracle (inputs: tests/urhand_cases.py, guarded on the CPU by tests/test_urhand_cases.py)
+def _hip(tag):
+    import urhand_cases as uc
+    from goliath_amd import uvlight
+
+    return uc.run_uv(uvlight, uc.uv_inputs(tag), lambda v: v.cuda())
+
+
+@pytest.mark.parametrize("tag", ["tail_unit", "tail_nosh", "nonunit", "highlight", "p0", "p1", "lowrough", "dark"])
+def test_uvlight_edge_shapes_vs_float64_oracle(tag):
+    """Multi-block launches with a partial tail at B > 1, P = 0 / 1 / 3 / 4 powers, non-unit normals (the upper halves of
+    clamp(n.L, 0, 1) and of min(s^p, 1)), a GGX lobe above 1, low roughness, zero total intensity: every output and every
+    input gradient of both kernels over ALL elements against the float64 oracle, bar max(1e-4, 1.5 e_ref64) per tensor
+    (e_ref64: what the float32 oracle itself is away from float64, tests/urhand_cases.py; measured there: at most 7.5e-5,
+    on ggx g_roughness of `nonunit`, so the bar is 1e-4 .. 1.13e-4).  Measured, HIP vs float64 (UV_EDGE lines), worst tensor
+    of each case: tail_unit 2.2e-5 (ggx g_nml), tail_nosh 5.8e-6, nonunit 7.1e-5 (ggx g_roughness; float32 oracle 7.5e-5),
+    highlight 6.2e-5 (ggx g_p_uv; float32 oracle 6.8e-5), p0 2.7e-6, p1 4.5e-6, lowrough 2.4e-5 (ggx g_roughness; float32 oracle
+    1.4e-5); every Phong tensor <= 6e-6."""
+    import urhand_cases as uc
+
+    got, ref, e64 = _hip(tag), uc.uv_oracle(tag, torch.float64), uc.e_ref64(tag)
+    c = uc.UV[tag]
+    B, H, W, P = c["B"], c["H"], c["W"], len(c["powers"])
+    assert got["phong/spec"].shape == (B, P, 1, H, W) and got["ggx/feat"].shape == (B, 1 + P, H, W)
+    fails = []
+    for k in uc.PHONG_KEYS + uc.GGX_KEYS:
+        assert got[k].shape == ref[k].shape and got[k].dtype == torch.float32, (tag, k)
+        assert bool(torch.isfinite(got[k]).all()), (tag, k)
+        if c.get("dark"):
+            assert not got[k].any() and not ref[k].any(), (tag, k)                # exactly 0, outputs and gradients
+            continue
+        e_hip, bar = rel_l2(got[k], ref[k]), max(TOL, 1.5 * e64[k][0])
+        print(f"\nUV_EDGE {tag} {k}: hip vs fp64 {e_hip:.2e}, fp32 reference vs fp64 {e64[k][0]:.2e}, bar {bar:.2e}")
+        if not e_hip < bar:
+            fails.append((k, e_hip, bar))
+    assert not fails, (tag, fails)
+
+
+def _args(tag, L=None):
+    import urhand_cases as uc
+
+    t = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in uc.uv_inputs(tag).items()}
+    if L is not None:
+        t["light_pos"], t["light_intensity"] = t["light_pos"][:, :L], t["light_intensity"][:, :L]
+        t["shadow_map"] = t["shadow_map"][:, :L]
+    return t
+
+
+def test_uvlight_no_lights():
+    """L == 0: Phong is an empty sum (zeros, zero gradients); GGX is a mean over lights and refuses, by an argument check
+    that returns before any launch."""
+    from goliath_amd import _lib, uvlight
+
+    t = _args("p1", L=0)
+    assert t["light_pos"].shape == (2, 0, 3) and t["shadow_map"].shape == (2, 0, 1, 9, 29)
+    p, n = t["p_uv"].clone().requires_grad_(True), t["nml"].clone().requires_grad_(True)
+    for sh in (t["shadow_map"], None):
+        d, s = uvlight.phong_features(p, n, t["cam_pos"], t["light_pos"], t["light_intensity"], sh, spec_powers=(1, 16))
+        assert d.shape == (2, 1, 9, 29) and s.shape == (2, 2, 1, 9, 29) and not d.any() and not s.any()
+        gp, gn = torch.autograd.grad(d.sum() + (s * 3.0).sum(), (p, n))
+        assert gp.shape == p.shape and not gp.any() and not gn.any()
+    with pytest.raises(_lib.GoliathHipError, match="L must be > 0"):
+        uvlight.ggx_features(p, n, t["cam_pos"], t["light_pos"], t["light_intensity"], t["roughness"], t["tex_mean"], None)
+    torch.cuda.synchronize()
+
+
+def test_uvlight_wrapper_forms():
+    """[B,L] and [B,L,1] intensities, a stride-0 expanded camera row, and a backward with one leaf only."""
+    import urhand_cases as uc
+    from goliath_amd import uvlight
+
+    t = _args("tail_unit")
+    base = uc.run_uv(uvlight, t, lambda v: v)
+    flat = uc.run_uv(uvlight, dict(t, light_intensity=t["light_intensity"][..., 0]), lambda v: v)
+    assert t["light_intensity"].dim() == 3 and all(torch.equal(base[k], flat[k]) for k in base)
+    one = dict(t, cam_pos=t["cam_pos"][:1].expand(3, 3))
+    assert one["cam_pos"].stride(0) == 0
+    a = uc.run_uv(uvlight, one, lambda v: v)
+    b = uc.run_uv(uvlight, dict(t, cam_pos=t["cam_pos"][:1].repeat(3, 1)), lambda v: v)
+    assert all(torch.equal(a[k], b[k]) for k in a) and not torch.equal(a["phong/spec"], base["phong/spec"])
+    # only nml requires grad
+    n = t["nml"].clone().requires_grad_(True)
+    fixed = (t["cam_pos"], t["light_pos"], t["light_intensity"])
+    d, s = uvlight.phong_features(t["p_uv"], n, *fixed, t["shadow_map"])
+    (g,) = torch.autograd.grad((d * t["w_diff"]).sum() + (s * t["w_spec"]).sum(), n)
+    assert torch.equal(g, base["phong/g_nml"])
+    f, rgb = uvlight.ggx_features(t["p_uv"], n, *fixed, t["roughness"], t["tex_mean"], t["shadow_map"])
+    (g,) = torch.autograd.grad((f * t["w_feat"]).sum() + (rgb * t["w_rgb"]).sum(), n)
+    assert torch.equal(g, base["ggx/g_nml"])
+
+
+def test_uvlight_rejects_powers_outside_the_domain():
+    """More than GOL_UV_MAX_POW powers, and any power below 1 (infinite derivative at s = 0 in the reference expression
+    too; at p = 0 the kernel's exp2(p log2 s) is NaN at s = 0, where torch.pow gives 1): ValueError before any launch."""
+    from goliath_amd import uvlight
+
+    t = _args("p1")
+    ph = lambda pw: uvlight.phong_features(t["p_uv"], t["nml"], t["cam_pos"], t["light_pos"], t["light_intensity"], None,
+                                           spec_powers=pw)
+    gg = lambda pw: uvlight.ggx_features(t["p_uv"], t["nml"], t["cam_pos"], t["light_pos"], t["light_intensity"],
+                                         t["roughness"], t["tex_mean"], None, spec_powers=pw)
+    for f in (ph, gg):
+        with pytest.raises(ValueError, match="at most 4"):
+            f((1, 2, 4, 8, 16))
+        for bad in ((0,), (1, 0.5), (16, -1.0), (float("nan"),)):
+            with pytest.raises(ValueError, match=">= 1"):
+                f(bad)
+        f((1.0,))          # the boundary itself is in the domain
+    torch.cuda.synchronize()
