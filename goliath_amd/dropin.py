@@ -7,6 +7,7 @@
     dropin.patch_geometry()       # optional: GeometryModule.to_uv / .vn and the decoder's postex / tn on the uvgeom kernels
     dropin.patch_lbs()            # optional: LinearBlendSkinning / LBSModule.pose on the fused skeleton + skinning kernels
     dropin.patch_relight_vis()    # optional, with patch_rgca(): run_vis_relight's frames from ONE render + the HIP env background
+    dropin.patch_sh()             # optional: sh.dir2sh_torch and (with patch_rgca()) the frame's light SH on ONE HIP launch, no host sync
 
 `install()` registers the module names the reference imports for its native code:
     gsplat            project_gaussians, rasterize_gaussians   (ca_code/utils/render_gsplat.py:10-11)
@@ -66,6 +67,42 @@ def patch_relight_vis(rgca_module=None):
         import ca_code.models.rgca as rgca_module
     setattr(rgca_module.AutoEncoder, fused.RELIGHT_VIS_FLAG, True)
     return rgca_module
+
+
+def patch_sh(sh_module=None, rgca_module=None):
+    """Opt in to the fused light path (goliath_amd.lights, csrc/lightsh.hip):
+      * `sh_module.dir2sh_torch` (ca_code/utils/sh.py:118-127: (deg+1)^2 functions evaluated one at a time, a device-to-host
+        sync each) is replaced by a wrapper that runs lights.dir2sh -- one launch, no sync -- for CUDA float32 directions
+        that need no gradient and deg <= 8; CPU tensors, other dtypes, deg > 8 and (with grad mode on) directions that
+        require grad go to the original, kept on the wrapper as `.reference`;
+      * a class flag on `AutoEncoder` and `PrimDecoder` (goliath_amd.rgca.LIGHT_SH_FLAG): with it the forwards
+        patch_rgca() installs take headrel_light_pos / headrel_light_sh from ONE gol_light_sh_fwd and the training-only
+        random light from lights.random_light_sh, under the same input conditions; without it they run the reference's
+        lines and call whatever `ca_code.utils.sh.dir2sh_torch` is.
+    Idempotent (patching twice does not wrap twice).  Returns (sh_module, rgca_module)."""
+    from . import lights
+    from . import rgca as fused
+
+    if sh_module is None:
+        import ca_code.utils.sh as sh_module
+    if rgca_module is None:
+        import ca_code.models.rgca as rgca_module
+    original = sh_module.dir2sh_torch
+    if not getattr(original, "_goliath_dir2sh", False):
+        import torch
+
+        def dir2sh_torch(deg, dirs):
+            if (torch.is_tensor(dirs) and dirs.is_cuda and dirs.dtype == torch.float32 and 0 <= deg <= lights.MAX_DEG
+                    and not (torch.is_grad_enabled() and dirs.requires_grad)):
+                return lights.dir2sh(deg, dirs)
+            return original(deg, dirs)
+
+        dir2sh_torch.reference = original
+        dir2sh_torch._goliath_dir2sh = True
+        sh_module.dir2sh_torch = dir2sh_torch
+    for cls in (rgca_module.AutoEncoder, rgca_module.PrimDecoder):
+        setattr(cls, fused.LIGHT_SH_FLAG, True)
+    return sh_module, rgca_module
 
 
 def patch_geometry(geom_module=None):

@@ -22,6 +22,12 @@ from .views import ViewSet
 
 
 RELIGHT_VIS_FLAG = "_goliath_relight_vis"   # class attribute of AutoEncoder set by dropin.patch_relight_vis()
+LIGHT_SH_FLAG = "_goliath_light_sh"         # class attribute of AutoEncoder and PrimDecoder set by dropin.patch_sh()
+
+
+def _fused_lights(*tensors) -> bool:
+    """The input conditions of goliath_amd.lights (dropin.patch_sh): CUDA float32, nothing to differentiate."""
+    return all(t.is_cuda and t.dtype == th.float32 and not (th.is_grad_enabled() and t.requires_grad) for t in tensors)
 
 
 def _fuse_projection() -> bool:
@@ -55,19 +61,29 @@ def autoencoder_forward(
     transforms as in :175-195, decode (the fused tail when `PrimDecoder.forward` is patched), ONE batched render, and
     ONE fused image pass for calibration + background composite + learnable blur (goliath_amd/imgtail.py) instead of a
     per-view Python loop, three elementwise kernels and two padded depthwise convolutions."""
-    import ca_code.utils.sh as sh  # the reference's SH basis (a handful of lights per view)
-
     from .imgtail import autoencoder_image_tail
 
+    frame_intensity = light_intensity
     light_intensity = light_intensity.expand(-1, -1, 3)
     rot, trans = head_pose[:, :3, :3], head_pose[:, :3, 3]
     bottom = th.zeros_like(head_pose[:, :1, :])
     bottom[:, 0, 3] = 1.0
     headrel_Rt = Rt @ th.cat([head_pose, bottom], dim=1)
     headrel_campos = ((campos - trans)[:, None] @ rot)[:, 0]
-    headrel_light_pos = (light_pos - trans[:, None]) @ rot
-    sh_coeffs = sh.dir2sh_torch(self.n_diff_sh, F.normalize(headrel_light_pos, p=2, dim=-1))
-    headrel_light_sh = (sh_coeffs[:, :, None] * light_intensity[..., None]).sum(dim=1)
+    if (getattr(self, LIGHT_SH_FLAG, False) and self.n_diff_sh <= 8 and frame_intensity.shape[-1] in (1, 3)
+            and tuple(head_pose.shape[1:]) == (3, 4) and _fused_lights(light_pos, frame_intensity, head_pose)):
+        # dropin.patch_sh(): both from ONE launch (gol_light_sh_fwd), no host sync
+        from .lights import headrel_light_sh as fused_light_sh
+
+        headrel_light_pos, headrel_light_sh = fused_light_sh(light_pos, frame_intensity, head_pose, self.n_diff_sh)
+    else:
+        # the reference's SH basis: (n_diff_sh + 1)^2 functions evaluated one at a time over ALL lights of the rig (the
+        # dataloader pads to n_lights_all), each a chain of small kernels that starts with a device-to-host sync (sh.py:55)
+        import ca_code.utils.sh as sh
+
+        headrel_light_pos = (light_pos - trans[:, None]) @ rot
+        sh_coeffs = sh.dir2sh_torch(self.n_diff_sh, F.normalize(headrel_light_pos, p=2, dim=-1))
+        headrel_light_sh = (sh_coeffs[:, :, None] * light_intensity[..., None]).sum(dim=1)
     if lightrot is not None:
         lightrot = lightrot @ rot
     enc_preds = self.encoder(registration_vertices, color)
@@ -199,8 +215,13 @@ def prim_decoder_forward(self, embs: th.Tensor, geom: th.Tensor, headrel_campos:
         f_vnocond, f_vcond = self.vnocond_mod(z), self.vcond_mod(zv)
 
     light_sh_rand, light_dir = None, None
-    if self.training:
-        import ca_code.utils.sh as sh  # the reference's SH basis (per-light, tiny)
+    if self.training and (getattr(self, LIGHT_SH_FLAG, False) and self.diff_sh_degree <= 8 and embs.is_cuda
+                          and headrel_light_pos.dtype == th.float32):
+        from .lights import random_light_sh as fused_random_light_sh   # dropin.patch_sh(): the same draw, one launch
+
+        light_dir, light_sh_rand = fused_random_light_sh(self.diff_sh_degree, B, embs.device, headrel_light_pos.dtype)
+    elif self.training:
+        import ca_code.utils.sh as sh  # the reference's SH basis (one light per view here, still 81 syncs)
 
         light_dir, light_sh_rand = random_light_sh(sh.dir2sh_torch, self.diff_sh_degree, B, embs.device,
                                                    headrel_light_pos.dtype)

@@ -872,6 +872,30 @@ int gol_envbg_image(int B, int H, int W, int He, int We, const float* envbg, con
 int gol_envbg_compose(int B, int H, int W, int He, int We, const float* render, const float* alpha, const float* bg,
                       const float* envbg, const float* R, int ball, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Light transform and SH light coefficients of a frame, forward only (csrc/lightsh.hip).  Replaces
+ * ca_code/models/rgca.py:175-191 (AutoEncoder.forward: headrel_light_pos, headrel_light_sh) and :590-613 (PrimDecoder.forward's
+ * random back-light) with what they call, ca_code/utils/sh.py:118-127 dir2sh_torch (81 functions evaluated one at a time,
+ * each with a device-to-host sync at sh.py:55).  Coefficient order: n = 0..deg outer, m = -n..n inner, index n*n + n + m;
+ * deg is 0 ... 8.  The reference's semantics (sh.py:54-103): the Legendre argument is clamp(z, -1, 1), sin(theta) =
+ * sqrt(max((1 + x)(1 - x), 1e-8)), phi = atan2(y, x) of the raw components (atan2(0, 0) = 0); Y = N cos(m phi) P_n^m for
+ * m > 0, N sin(|m| phi) P_n^|m| for m < 0, N P_n^0 for m = 0, with P by the upward recurrences of sh.py:58-78.
+ * gol_sh_norm_constants: host code, no GPU.  The (deg+1)^2 constants N in float64: KVal(|m|, n) = sqrt((2n + 1) / (4 pi)
+ *   (n - |m|)! / (n + |m|)!) (sh.py:13-26), times sqrt(2) for m != 0 (sh.py:80-86).  The kernels use these rounded to float32.
+ * gol_sh_basis_fwd: dirs[M,3] -> coeffs[M,(deg+1)^2] = dir2sh_torch(deg, dirs); dirs are NOT normalised (as there).
+ * gol_light_sh_fwd: light_pos[B,L,3], light_intensity[B,L,intensity_channels] (1 = the reference's .expand(-1, -1, 3), or
+ *   3), head_pose[B,3,4] = [R | t] (NULL = identity).  headrel_light_pos[B,L,3] = (p - t) @ R (NULL = not wanted);
+ *   light_sh[B,3,(deg+1)^2][b,c,k] = sum_l Y_k(d_l) I[b,l,c] with d_l = F.normalize(headrel_light_pos[b,l]) =
+ *   v / max(|v|, 1e-12) (a zero vector stays zero).  The sum runs in light order into one accumulator per output through
+ *   LDS: a light of zero intensity (the dataloader's padding) contributes exactly nothing.
+ * Every output is finite for finite input.  One launch each, no host sync, no allocation, no atomics: bitwise
+ * reproducible, graph-capturable.  M * 81 < 2^31, B * L * 3 < 2^31.
+ * ---------------------------------------------------------------------------------------- */
+int gol_sh_norm_constants(int deg, double* out /* [(deg+1)^2] */);
+int gol_sh_basis_fwd(int M, int deg, const float* dirs, float* coeffs, void* stream);
+int gol_light_sh_fwd(int B, int L, int deg, const float* light_pos, const float* light_intensity, int intensity_channels,
+                     const float* head_pose, float* headrel_light_pos, float* light_sh, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
