@@ -241,7 +241,9 @@ __device__ __forceinline__ EnvSample env_lookup(const gol_shade_in& in, int b, f
     s1 = s0;
     if (q > 1) s1 = bilinear_border<false>(m1 + (size_t)b * 3 * h1 * w1, h1, w1, u, v);
   }
-  const float msc = in.mips_scale != 0.f ? in.mips_scale : 1.f;  // the driver's per-frame scale of the whole pyramid
+  // the driver's per-frame scale of the whole pyramid: the host float, or -- mips_scale_dev -- a float the frame's own
+  // kernels left in device memory (gol_envspin_frame: no host read of it).  One wave-uniform load, issued behind the gathers
+  const float msc = in.mips_scale_dev ? *in.mips_scale_dev : (in.mips_scale != 0.f ? in.mips_scale : 1.f);
   if (q > 1) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {

@@ -8,6 +8,7 @@
     dropin.patch_lbs()            # optional: LinearBlendSkinning / LBSModule.pose on the fused skeleton + skinning kernels
     dropin.patch_relight_vis()    # optional, with patch_rgca(): run_vis_relight's frames from ONE render + the HIP env background
     dropin.patch_sh()             # optional: sh.dir2sh_torch and (with patch_rgca()) the frame's light SH on ONE HIP launch, no host sync
+    dropin.patch_env_driver()     # optional: EnvSpinDecorator.forward's per-frame map rotation, light probe and mip scale on the GPU
 
 `install()` registers the module names the reference imports for its native code:
     gsplat            project_gaussians, rasterize_gaussians   (ca_code/utils/render_gsplat.py:10-11)
@@ -160,7 +161,9 @@ def _shared_mipmap(self, bsize, device, scale=1.0):
                 del cache[k]                         # the buffer was replaced / rewritten: drop the stale device copy
             base = cache[key] = buf.to(device)
         m = (base * scale).expand(bsize, -1, -1, -1)
-        m._gol_base, m._gol_scale = base, float(scale)
+        # a CUDA tensor (envdriver's mip_scale) stays one: `base * scale` above was a device multiply, and shade hands the
+        # tensor's address to the kernel instead of waiting for its value
+        m._gol_base, m._gol_scale = base, scale if getattr(scale, "is_cuda", False) else float(scale)
         out.append(m)
     return out
 
@@ -171,6 +174,76 @@ def patch_light_decorator(decorator_module=None):
     if decorator_module is None:
         import ca_code.utils.light_decorator as decorator_module
     decorator_module.EnvSpinDecorator.mipmap = _shared_mipmap
+    return decorator_module
+
+
+def _env_spin_state(self, device):
+    """The decorator's goliath_amd.envdriver.EnvSpin, built lazily from `self.image` and rebuilt when the image (address,
+    in-place version), the device or one of the scalars it bakes in changes.  None: this decorator stays on the reference
+    (no GPU, or perc90 <= 0 -- the reference then divides by the maximum of every rotated frame, light_decorator.py:125)."""
+    import numpy as np
+
+    from . import envdriver
+
+    key = (self.image.data_ptr(), self.image._version, str(device), float(self.env_scale), self.cycle,
+           float(self.envmap_dist))
+    hit = self.__dict__.get("_gol_env_spin")
+    if hit is None or hit[0] != key:
+        state = None
+        if device.type == "cuda":
+            perc90 = np.percentile(self.image.data.cpu().numpy(), 90)
+            if perc90 > 0:
+                state = envdriver.EnvSpin(self.image, self.env_scale, cycle=self.cycle, envmap_dist=self.envmap_dist,
+                                          perc90=perc90, device=device)
+        hit = self.__dict__["_gol_env_spin"] = (key, state)
+    return hit[1]
+
+
+def _env_driver_forward(self, reference, **data):
+    """EnvSpinDecorator.forward (ca_code/utils/light_decorator.py:102-164) on goliath_amd.envdriver: the same keys, shapes
+    and dtypes in `data`, from three launches per frame instead of a CPU grid_sample, a percentile, a CPU interpolate and a
+    6 MB upload per view.  `preconv_envmap` comes from self.mipmap with the frame's scale as a DEVICE tensor (with
+    patch_light_decorator() the shading kernel reads it from there)."""
+    import torch
+
+    device = data["campos"].device
+    batch_size = data["campos"].size(0)
+    state = _env_spin_state(self, device)
+    if state is None:
+        return reference(self, **data)
+    index = data["index"]
+    index = index[:batch_size] if torch.is_tensor(index) else [index[i] for i in range(batch_size)]
+    with torch.no_grad():
+        fr = state.frame(index=index)
+    data["preconv_envmap"] = self.mipmap(batch_size, device, fr.mip_scale)
+    data["sigma_step"] = self.sigma_step
+    data["envmap"] = fr.envmap
+    data["lightrot"] = fr.lightrot
+    data["light_intensity"] = fr.light_intensity
+    data["light_pos"] = fr.light_pos
+    data["envbg"] = fr.envbg
+    data["light_type"] = "envmap"
+    data["n_lights"] = fr.n_lights
+    data["is_fullylit_frame"] = torch.zeros(1, device=device)
+    return self.mod(**data)
+
+
+def patch_env_driver(decorator_module=None):
+    """Opt in to the fused relight driver: `EnvSpinDecorator.forward` becomes _env_driver_forward; the original stays on it
+    as `.reference` and still serves a decorator whose np.percentile(image, 90) is not positive.  Implies none of the other
+    patches and changes no default path; idempotent.  A sync-free loop also needs GOLIATH_CHECK_LIGHTROT=0.
+    Returns the patched module."""
+    if decorator_module is None:
+        import ca_code.utils.light_decorator as decorator_module
+    cls = decorator_module.EnvSpinDecorator
+    original = cls.forward
+    if not getattr(original, "_goliath_env_driver", False):
+        def forward(self, **data):
+            return _env_driver_forward(self, original, **data)
+
+        forward.reference = original
+        forward._goliath_env_driver = True
+        cls.forward = forward
     return decorator_module
 
 

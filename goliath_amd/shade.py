@@ -28,7 +28,8 @@ class ShadeIn(ctypes.Structure):
                 ("n_mips", ctypes.c_int32), ("mips", _fp * MAX_MIPS), ("mip_h", ctypes.c_int32 * MAX_MIPS),
                 ("mip_w", ctypes.c_int32 * MAX_MIPS), ("lightrot", _fp), ("mips_packed", _fp * MAX_MIPS),
                 ("primscale_min", ctypes.c_float),
-                ("primscale_max", ctypes.c_float), ("mips_shared", ctypes.c_int32), ("mips_scale", ctypes.c_float)]
+                ("primscale_max", ctypes.c_float), ("mips_shared", ctypes.c_int32), ("mips_scale", ctypes.c_float),
+                ("mips_scale_dev", _fp)]
 
 
 OUT_FIELDS = [("color", 3), ("opacity", 1), ("primpos", 3), ("primqvec", 4), ("primscale", 3),
@@ -119,7 +120,10 @@ def _make_in(f_vnocond, f_vcond, postex, tn, albedo, light_sh, light_sh_rand, ca
                 s.mips_packed[i] = _p(packed[i])
         s.lightrot = _p(lightrot)
         s.mips_shared = int(shared)
-        s.mips_scale = float(mips_scale)
+        if torch.is_tensor(mips_scale):     # the frame's scale stays in device memory (gol_shade_in.mips_scale_dev)
+            s.mips_scale_dev = _p(mips_scale)
+        else:
+            s.mips_scale = float(mips_scale)
         if not shared and any(m.shape[0] != B for m in mips):
             raise ValueError(f"env-map levels must be [B={B},3,h,w] (one pyramid per view) or [1,3,h,w] (one for all views)")
     else:
@@ -246,6 +250,13 @@ def _check_rotation(lightrot):
     _ROT_CHECKED[key] = weakref.ref(lightrot)
 
 
+def _device_scale(scales):
+    """Every level carries the SAME 1-element CUDA float32 tensor as its scale."""
+    s0 = scales[0]
+    return (torch.is_tensor(s0) and s0.is_cuda and s0.dtype == torch.float32 and s0.numel() == 1
+            and all(s is s0 for s in scales))
+
+
 def shading_tail(f_vnocond, f_vcond, postex, tn, albedo, headrel_light_sh, headrel_campos,
                  light_intensity=None, headrel_light_pos=None, n_lights=None, preconv_envmap=None,
                  lightrot=None, light_sh_rand=None, n_color_sh=3, n_diff_sh=8, views=None):
@@ -285,9 +296,15 @@ def shading_tail_coefs(f_vnocond, f_vcond, postex, tn, albedo, headrel_light_sh,
                 raise ValueError(f"env-map levels are expanded over {[m.shape[0] for m in mips]} views, the batch has {B}")
             # levels that come from dropin._shared_mipmap carry the UNSCALED registered buffer and the frame's scale: the
             # packed records are cached on the buffer (stable address and version across frames), the scale goes to the kernel
+            # -- a float, or ONE 1-element CUDA float32 tensor carried by every level (envdriver's mip_scale: the kernel reads
+            # it from device memory, nothing here waits for its value)
             base = [getattr(m, "_gol_base", None) for m in mips]
-            if all(b is not None for b in base) and len({float(m._gol_scale) for m in mips}) == 1:
-                mips_scale, mips = float(mips[0]._gol_scale), base
+            scales = [getattr(m, "_gol_scale", None) for m in mips]
+            if all(b is not None for b in base) and _device_scale(scales):
+                mips_scale, mips = scales[0], base
+            elif (all(b is not None for b in base) and not any(torch.is_tensor(s) for s in scales)
+                  and len({float(s) for s in scales}) == 1):
+                mips_scale, mips = float(scales[0]), base
             else:
                 mips = [m[:1] for m in mips]
         mips = [c(m) for m in mips]

@@ -306,6 +306,11 @@ typedef struct {
    * the registered pyramid by 2 pi norm_scale[0] per FRAME (light_decorator.py:147-149): with the factor here the unscaled
    * pyramid is packed once per environment and nothing is re-packed when the spin index changes. */
   float mips_scale;
+  /* NULL (the default): the host float above.  Otherwise one float in device memory, read by the kernels in place of
+   * mips_scale (which is then ignored; the value is used as it is, 0 included): the relight driver's 2 pi norm_scale[0]
+   * (light_decorator.py:151-153) as gol_envspin_frame leaves it, so that no host code waits for the frame's scale.  All four
+   * entries (forward, backward, both *_project_*) read it. */
+  const float* mips_scale_dev;
 } gol_shade_in;
 
 typedef struct {  /* every field [B,N,k] row-major like the reference's preds (rgca.py:574-588) */
@@ -895,6 +900,45 @@ int gol_sh_norm_constants(int deg, double* out /* [(deg+1)^2] */);
 int gol_sh_basis_fwd(int M, int deg, const float* dirs, float* coeffs, void* stream);
 int gol_light_sh_fwd(int B, int L, int deg, const float* light_pos, const float* light_intensity, int intensity_channels,
                      const float* head_pose, float* headrel_light_pos, float* light_sh, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The per-frame work of the env-relight driver, forward only (csrc/envdriver.hip).  Replaces
+ * ca_code/utils/light_decorator.py:120-143 (EnvSpinDecorator.forward, per view) with what it calls,
+ * ca_code/utils/envmap.py:141-166 rotate_envmap_mat: a CPU grid_sample of the whole map, a percentile of it, an antialiased
+ * CPU interpolate to the 16 x 32 light probe and a 6 MB upload per view.  At most three launches per call, any B.
+ * gol_envspin_frame parameters:
+ *   B, H, W          views (light_decorator.py:109 batch_size) and the size of the map (:58: 512 x 1024); H >= 16, W >= 32,
+ *                    W even (envmap.py:149 arange(-W//2, W//2)), else GOL_ERR_INVALID_ARG
+ *   image[3,H,W]     self.image (:61-62), the unrotated map, on the device
+ *   rot[B,9]         rot_mat (:119) of every view, row-major
+ *   tap_y_start[16], tap_y_w[16,ky], tap_x_start[32], tap_x_w[32,kx]
+ *                    thf.interpolate(new_env[None], (16, 32), mode="bilinear", antialias=True) (:128-130) as two 1-D tables:
+ *                    per output row (column) the first source row (column) with a non-zero weight and its ky (kx) weights
+ *                    from there on, padded with zeros, in double; probe[c,i,j] = sum wy[i][a] wx[j][b] new_env[c, ys_i + a,
+ *                    xs_j + b].  Source indices are clamped to the map by the kernel.
+ *   perc90           np.percentile(self.image, 90) (:123), > 0
+ *   env_scale        self.env_scale (:138-139)
+ *   scratch          gol_envspin_scratch_floats(B,H,W) floats, 8-byte aligned (16 for the vector stores)
+ *   envbg[B,3,H,W]   ((new_env / perc90) * 255) / 255 (:124-126, :159), each operation rounded to float32; NULL = not wanted
+ *   envmap[B,3,16,32]          env_scale probe / S_b, S_b = sum probe sin((i + 0.5) pi / 16) (:132-141)
+ *   light_intensity[B,512,3]   the same values, new_env.view(3, -1).t() (:143)
+ *   norm_scale[B]              env_scale / S_b (:139)
+ *   mip_scale[1]               2 pi env_scale / S_0 = 2 pi norm_scale[0], the `scale` of self.mipmap (:151-153), formed in
+ *                              double and rounded once (the reference multiplies two float32 numbers: up to an ulp more error);
+ *                              what gol_shade_in.mips_scale_dev points at
+ * new_env is envmap.py:147-164 as written: theta = (y + 0.5) 3.1415926 / H, phi = (x - W/2 + 0.5) 3.1415926 2 / W,
+ * vec = (sin theta sin phi, cos theta, sin theta cos phi), d = rot vec (:154-155 matmul(vec, rot_mat.T)), clamped to
+ * [-1, 1], u = atan2(dx, dz) / pi, v = 2 acos(dy) / pi - 1, grid_sample(bilinear, align_corners=False,
+ * padding_mode="border"): ix = ((u + 1) W - 1) / 2 clipped to [0, W - 1] (the u = +-1 seam clamps, it does not wrap).
+ * Angles, position and blend are evaluated in double and rounded once; the probe and S_b are double sums over the float32
+ * new_env in a fixed order.  No host sync, no allocation, no atomics: two calls are bitwise equal, view b of a batch equals
+ * the same view alone, and the call captures as a graph of one linear chain.
+ * ---------------------------------------------------------------------------------------- */
+int64_t gol_envspin_scratch_floats(int B, int H, int W);
+int gol_envspin_frame(int B, int H, int W, const float* image, const float* rot, const int32_t* tap_y_start,
+                      const double* tap_y_w, int ky, const int32_t* tap_x_start, const double* tap_x_w, int kx,
+                      float perc90, double env_scale, float* scratch, float* envbg, float* envmap, float* light_intensity,
+                      float* norm_scale, float* mip_scale, void* stream);
 
 #ifdef __cplusplus
 }
