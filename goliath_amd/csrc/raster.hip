@@ -26,6 +26,8 @@
 
 namespace {
 
+constexpr int kBgGroup = 4;   // tiles per group of the forward's empty-run path (2, 4 and 8 are built; see gol_rasterize_fwd)
+
 // Forward.  One workgroup per 16x16 tile (PPL = 2: 128 threads, PPL = 1: 256; see Pix).
 // LAZY (the fused path, planar images): everything that only changes when a pixel STOPS -- its liveness, the index the
 // backward may start from, the "is this half finished" test -- moves out of the per-visit instruction stream into a
@@ -42,7 +44,7 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_fwd_kernel(
     float* __restrict__ out_extra, float* __restrict__ final_Ts, int32_t* __restrict__ final_idx,
     float* __restrict__ out_alpha, float* __restrict__ out_extra_norm, float norm_lo,
     const float* __restrict__ l1_target, const float* __restrict__ l1_mask, int l1_mask_c,
-    uint8_t* __restrict__ l1_sign, float* __restrict__ l1_partial, int n_views) {
+    uint8_t* __restrict__ l1_sign, float* __restrict__ l1_partial, int n_views, int bg_group, int bg_vec16) {
   typedef typename Pix<PPL>::fv fv;
   typedef typename Pix<PPL>::iv iv;
   constexpr int NW = Pix<PPL>::kWaves, NT = 64 * NW;
@@ -63,6 +65,137 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_fwd_kernel(
   const TileCoord tc = tile_of_block(slot, T, tiles_x);
   if (!tc.ok) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  // Runs of empty tiles (bg_group = G > 0: planar images of even width, see gol_rasterize_fwd).  A group is G consecutive
+  // tiles of one tile row -- consecutive workgroups of one die (tile_of_block).  Every workgroup reads the group's G list
+  // ranges (wave-uniform: scalar loads).  Some tile has entries: all of them run the per-tile code below, unchanged.  The
+  // whole group is empty: its first workgroup writes the constant outputs of the WHOLE region as full rows (8 or 16 bytes
+  // per lane instead of 4-byte accesses to 64-byte row segments) and sums the fused L1 of every tile; the others return at
+  // once -- they neither hold a workgroup place through two memory round trips nor touch the image.  The constants are formed
+  // with the per-tile epilogue's expressions and the L1 keeps its lane-to-pixel map and order of additions: same bits.
+  int2 range;   // the tile's own list range (with groups: picked from the group's ranges, no second round trip)
+  auto fill_group = [&](auto g_c) -> bool {
+    constexpr int G = decltype(g_c)::value;
+    const int tx0 = tc.tx & ~(G - 1), n = min(G, tiles_x - tx0);
+    const size_t tile0 = (size_t)view * T + (size_t)(tc.tile - (tc.tx - tx0));
+    int entries = 0;
+#pragma unroll
+    for (int t = 0; t < G; ++t) {
+      const int2 r = tile_bins[tile0 + min(t, n - 1)];
+      entries |= (r.y > r.x) ? 1 : 0;
+      if (t == tc.tx - tx0) range = r;
+    }
+    if (entries) return false;
+    if (tc.tx != tx0) return true;
+    const unsigned hw = (unsigned)img_h * (unsigned)img_w;
+    const size_t vplane = (size_t)view * hw;
+    const float Tq = 1.f, ex = 0.f;
+    const float c0 = 0.f + Tq * background[0], c1 = 0.f + Tq * background[1], c2 = 0.f + Tq * background[2];
+    const float al = 1.f - Tq;
+    const float nrm = ex / fminf(fmaxf(1.f - Tq, norm_lo), 1.f);
+    float* __restrict__ o_T = final_Ts + vplane;
+    float* __restrict__ o_img = out_img + 3 * vplane;
+    float* __restrict__ o_img1 = o_img + hw;
+    float* __restrict__ o_img2 = o_img + 2u * hw;
+    float* __restrict__ o_ex = (EXTRA && out_extra) ? out_extra + vplane : nullptr;
+    float* __restrict__ o_alpha = out_alpha ? out_alpha + vplane : nullptr;
+    float* __restrict__ o_norm = (EXTRA && out_extra_norm) ? out_extra_norm + vplane : nullptr;
+    const int x0 = tx0 * 16, y0 = tc.ty * 16;
+    const int rw = min(x0 + 16 * G, img_w) - x0, nrows = min(16, img_h - y0);   // rw: a multiple of the store width
+    auto fill_rows = [&](auto v_c) {
+      constexpr int V = decltype(v_c)::value;               // floats per lane and store
+      typedef float vt __attribute__((ext_vector_type(V)));
+      typedef int it __attribute__((ext_vector_type(V)));
+      constexpr int CPR = 16 * G / V, RPP = NT / CPR;       // lanes along a full row; rows per pass of the workgroup
+      const int col = (tid % CPR) * V, r0 = tid / CPR;
+#pragma unroll
+      for (int k = 0; k * RPP < 16; ++k) {
+        const int r = r0 + k * RPP;
+        if (col < rw && r < nrows) {
+          const unsigned b4 = ((unsigned)(y0 + r) * (unsigned)img_w + (unsigned)(x0 + col)) * 4u;
+          *reinterpret_cast<vt*>(gol_at(o_T, b4)) = vt(Tq);
+          if (!LAZY) *reinterpret_cast<it*>(gol_at(final_idx + vplane, b4)) = it(0);   // gsplat's exact final_idx
+          *reinterpret_cast<vt*>(gol_at(o_img, b4)) = vt(c0);
+          *reinterpret_cast<vt*>(gol_at(o_img1, b4)) = vt(c1);
+          *reinterpret_cast<vt*>(gol_at(o_img2, b4)) = vt(c2);
+          if (o_ex) *reinterpret_cast<vt*>(gol_at(o_ex, b4)) = vt(ex);
+          if (o_alpha) *reinterpret_cast<vt*>(gol_at(o_alpha, b4)) = vt(al);
+          if (o_norm) *reinterpret_cast<vt*>(gol_at(o_norm, b4)) = vt(nrm);
+        }
+      }
+    };
+    if (bg_vec16) fill_rows(std::integral_constant<int, 4>());
+    else fill_rows(std::integral_constant<int, 2>());
+    if (!l1_target) return true;
+    // fused L1 of the group's tiles: the target (and mask) values of up to four tiles are in flight before the first is used
+    // (all of a group of two or four; eight tiles x two pixels per lane x six values would cost the kernel a wave per SIMD)
+    const float* __restrict__ i_tgt = l1_target + 3 * vplane;
+    const float* __restrict__ i_mask = l1_mask ? l1_mask + (size_t)l1_mask_c * vplane : nullptr;
+    float* s_part = reinterpret_cast<float*>(s_a);           // [G][NW] wave sums (the batch arrays are idle on this path)
+    constexpr int CH = G < 4 ? G : 4;
+    auto l1_tiles = [&](auto m_c) {
+      constexpr int MC = decltype(m_c)::value;               // mask channels: 0 (none), 1 or 3
+      const float cs[3] = {c0, c1, c2};
+#pragma unroll
+      for (int tb = 0; tb < G; tb += CH) {
+        if (tb >= n) break;
+        float tg[CH][PPL][3], mk[CH][PPL][3];
+        bool ok[CH][PPL];
+#pragma unroll
+        for (int t = 0; t < CH; ++t) {
+          int tj, ti0;
+          lane_pixel<PPL>(tx0 + tb + t, tc.ty, wave, lane, tj, ti0);
+#pragma unroll
+          for (int q = 0; q < PPL; ++q) {
+            ok[t][q] = (ti0 + q < img_h) && (tj < img_w);
+            // a pixel outside the image (or in a tile past the row's end) reads the nearest pixel inside and is dropped below
+            const unsigned b4 = ((unsigned)min(ti0 + q, img_h - 1) * (unsigned)img_w + (unsigned)min(tj, img_w - 1)) * 4u;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              tg[t][q][c] = *gol_at(i_tgt + (size_t)c * hw, b4);
+              mk[t][q][c] = MC == 0 ? 1.f : (MC == 3 || c == 0) ? *gol_at(i_mask + (size_t)c * hw, b4) : mk[t][q][0];
+            }
+          }
+        }
+#pragma unroll
+        for (int t = 0; t < CH; ++t) {
+          float l1_acc = 0.f;
+#pragma unroll
+          for (int q = 0; q < PPL; ++q) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              const float d = (cs[c] - tg[t][q][c]) * mk[t][q][c];
+              l1_acc += ok[t][q] ? fabsf(d) : 0.f;
+            }
+          }
+          const float ws = gol_wave_sum_to_lane63(l1_acc);
+          if (lane == 63) s_part[(tb + t) * NW + wave] = ws;
+        }
+      }
+    };
+    if (!i_mask) l1_tiles(std::integral_constant<int, 0>());
+    else if (l1_mask_c == 3) l1_tiles(std::integral_constant<int, 3>());
+    else l1_tiles(std::integral_constant<int, 1>());
+    __syncthreads();
+    if (tid < n) {
+      float tot = 0.f;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) tot += s_part[tid * NW + w];
+      l1_partial[tile0 + tid] = tot;
+    }
+    return true;
+  };
+  // (two pixels per lane only: launches of one or two views, which take the four-wave layout, last as long as their longest
+  // list's chain and gain nothing from the groups, while the larger kernel ran 6 % longer -- profiles/raster_fwd_bg_ab.txt)
+  if (PPL == 2 && bg_group) {   // (kernel-uniform)
+    const bool done = bg_group == 2 ? fill_group(std::integral_constant<int, 2>())
+                    : bg_group == 4 ? fill_group(std::integral_constant<int, 4>())
+                                    : fill_group(std::integral_constant<int, 8>());
+    if (done) return;
+  } else {
+    range = tile_bins[(size_t)view * T + tc.tile];
+  }
+
   int j, i0;
   lane_pixel<PPL>(tc.tx, tc.ty, wave, lane, j, i0);
   bool in[PPL];
@@ -79,7 +212,6 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_fwd_kernel(
   }
   const float px = (float)j + 0.5f;
 
-  const int2 range = tile_bins[(size_t)view * T + tc.tile];
   const int32_t* ids = sorted_ids + (size_t)view * capacity;
   const size_t goff = (size_t)view * N;
 
@@ -664,6 +796,23 @@ extern "C" int gol_rasterize_fwd(int B, int N, int img_h, int img_w, int block, 
   // through one wave, which the finer footprint shortens to ~0.55x for ~9 % more instructions in total (see Pix)
   int ppl = pixels_per_lane;
   if (ppl == 0) gol_raster_plan(B, &ppl);
+  // Runs of empty tiles are filled by one workgroup per group of bg_group tiles (see raster_fwd_kernel).  GOL_RASTER_BG_GROUP
+  // = 0 | 2 | 4 | 8 overrides the group size; it is read on every call (A/B runs and the parity test switch it inside one
+  // process).  The row stores are 16 bytes per lane where every row of every plane starts on a 16-byte boundary, else 8; an
+  // odd width, gsplat's interleaved layout, a plane that is not 8-byte aligned and the four-wave layout (one pixel per lane)
+  // keep the per-tile epilogue.
+  int bg_group = kBgGroup, bg_vec16 = 0;
+  if (const char* e = getenv("GOL_RASTER_BG_GROUP")) bg_group = atoi(e);
+  GOL_REQUIRE(bg_group == 0 || bg_group == 2 || bg_group == 4 || bg_group == 8, "GOL_RASTER_BG_GROUP: 0, 2, 4 or 8");
+  if (!planar || (img_w & 1) || ppl != 2) bg_group = 0;
+  if (bg_group) {
+    uintptr_t bits = 0;
+    for (const void* p : {(const void*)out_img, (const void*)final_Ts, (const void*)out_extra, (const void*)out_alpha,
+                          (const void*)out_extra_norm})
+      bits |= reinterpret_cast<uintptr_t>(p);
+    bg_vec16 = (img_w % 4 == 0 && bits % 16 == 0) ? 1 : 0;
+    if (bits % 8 != 0) bg_group = 0;
+  }
   auto launch = [&](auto ex_c, auto lazy_c) {
     with_ppl(ppl, [&](auto ppl_c) {
       constexpr bool EX = decltype(ex_c)::value, LZ = decltype(lazy_c)::value;
@@ -671,7 +820,7 @@ extern "C" int gol_rasterize_fwd(int B, int N, int img_h, int img_w, int block, 
       raster_fwd_kernel<EX, LZ, PPL><<<grid, 64 * Pix<PPL>::kWaves, 0, s>>>(
           N, img_h, img_w, planar, tiles_x, tiles_y, bins, sorted_ids, capacity, records, background, out_img, out_extra,
           final_Ts, final_idx, out_alpha, EX ? out_extra_norm : nullptr, norm_lo, l1_target, l1_mask, l1_mask_c, l1_sign,
-          l1_partial, B);
+          l1_partial, B, bg_group, bg_vec16);
     });
   };
   const bool ex = out_extra || out_extra_norm;
