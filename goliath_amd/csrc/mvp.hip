@@ -194,12 +194,15 @@ struct Ray {
 
 struct Tri { int idx[8]; float w[8]; float fx, fy, fz; int x0, y0, z0; bool allv; };
 
-// utils.h:523-560 (align_corners=True coordinates, zero padding): corner indices (-1 = outside) + weights, for a
-// position strictly inside the box (valid_pos: every sample the march evaluates).  Then (pos + 1) / 2 is in (0, 1) and
-// the floor of the voxel coordinate in [0, W-1], so the lower corner always exists and the upper one of an axis is
-// missing only when the coordinate rounded up to W-1 exactly: three compares decide all eight corners (the general
-// form tested 6 bounds per corner).  Executed by every lane (the clamp keeps the integers defined for the positions of
-// lanes that do not evaluate; their indices are never used).
+// utils.h:523-560 (align_corners=True coordinates, zero padding): corner indices (-1 = outside) + weights.
+// INSIDE: for a position strictly inside the box (valid_pos: every sample the march evaluates).  Then (pos + 1) / 2 is in
+// (0, 1) and the floor of the voxel coordinate in [0, W-1], so the lower corner always exists and the upper one of an axis is
+// missing only when the coordinate rounded up to W-1 exactly: three compares decide all eight corners.
+// !INSIDE: for an ARBITRARY position (warp fields, algo 1: the template is sampled at the warped position, which may leave
+// the box): every corner tested against all six bounds.
+// Executed by every lane (the clamp keeps the integers defined for the positions of lanes that do not evaluate; their
+// indices are never used).
+template <bool INSIDE>
 __device__ __forceinline__ void tri_setup(Tri& q, int D, int H, int W, V3 pos) {
   const float ix = fmaxf(-100.f, fminf(100.f, (pos.x + 1.f) * 0.5f)) * (float)(W - 1);
   const float iy = fmaxf(-100.f, fminf(100.f, (pos.y + 1.f) * 0.5f)) * (float)(H - 1);
@@ -207,44 +210,30 @@ __device__ __forceinline__ void tri_setup(Tri& q, int D, int H, int W, V3 pos) {
   const float fx0 = floorf(ix), fy0 = floorf(iy), fz0 = floorf(iz);
   const int x0 = (int)fx0, y0 = (int)fy0, z0 = (int)fz0;
   q.fx = ix - fx0; q.fy = iy - fy0; q.fz = iz - fz0; q.x0 = x0; q.y0 = y0; q.z0 = z0;
-  const bool vx = x0 + 1 < W, vy = y0 + 1 < H, vz = z0 + 1 < D;
-  q.allv = vx && vy && vz;  // all eight corners exist (always, but for a coordinate that rounded up to the last voxel)
   const int sy = W, sz = H * W;
   const int b = z0 * sz + y0 * sy + x0;
-  q.idx[0] = b;
-  q.idx[1] = vx ? b + 1 : -1;
-  q.idx[2] = vy ? b + sy : -1;
-  q.idx[3] = (vx && vy) ? b + sy + 1 : -1;
-  q.idx[4] = vz ? b + sz : -1;
-  q.idx[5] = (vx && vz) ? b + sz + 1 : -1;
-  q.idx[6] = (vy && vz) ? b + sz + sy : -1;
-  q.idx[7] = (vx && vy && vz) ? b + sz + sy + 1 : -1;
-  const float gx = 1.f - q.fx, gy = 1.f - q.fy, gz = 1.f - q.fz;
-  const float w00 = gx * gy, w10 = q.fx * gy, w01 = gx * q.fy, w11 = q.fx * q.fy;
-  q.w[0] = w00 * gz; q.w[1] = w10 * gz; q.w[2] = w01 * gz; q.w[3] = w11 * gz;
-  q.w[4] = w00 * q.fz; q.w[5] = w10 * q.fz; q.w[6] = w01 * q.fz; q.w[7] = w11 * q.fz;
-}
-
-// The same for an ARBITRARY position (warp fields, algo 1: the template is sampled at the warped position, which may
-// leave the box): every corner tested against all six bounds (utils.h:523-560).
-__device__ __forceinline__ void tri_setup_any(Tri& q, int D, int H, int W, V3 pos) {
-  const float ix = fmaxf(-100.f, fminf(100.f, (pos.x + 1.f) * 0.5f)) * (float)(W - 1);
-  const float iy = fmaxf(-100.f, fminf(100.f, (pos.y + 1.f) * 0.5f)) * (float)(H - 1);
-  const float iz = fmaxf(-100.f, fminf(100.f, (pos.z + 1.f) * 0.5f)) * (float)(D - 1);
-  const float fx0 = floorf(ix), fy0 = floorf(iy), fz0 = floorf(iz);
-  const int x0 = (int)fx0, y0 = (int)fy0, z0 = (int)fz0;
-  q.fx = ix - fx0; q.fy = iy - fy0; q.fz = iz - fz0; q.x0 = x0; q.y0 = y0; q.z0 = z0;
-  const bool vx[2] = {x0 >= 0 && x0 < W, x0 + 1 >= 0 && x0 + 1 < W};
-  const bool vy[2] = {y0 >= 0 && y0 < H, y0 + 1 >= 0 && y0 + 1 < H};
-  const bool vz[2] = {z0 >= 0 && z0 < D, z0 + 1 >= 0 && z0 + 1 < D};
-  const int sy = W, sz = H * W;
-  const int b = z0 * sz + y0 * sy + x0;
-  q.allv = true;
+  if (INSIDE) {
+    const bool vx = x0 + 1 < W, vy = y0 + 1 < H, vz = z0 + 1 < D;
+    q.allv = vx && vy && vz;  // all eight corners exist (always, but for a coordinate that rounded up to the last voxel)
+    q.idx[0] = b;
+    q.idx[1] = vx ? b + 1 : -1;
+    q.idx[2] = vy ? b + sy : -1;
+    q.idx[3] = (vx && vy) ? b + sy + 1 : -1;
+    q.idx[4] = vz ? b + sz : -1;
+    q.idx[5] = (vx && vz) ? b + sz + 1 : -1;
+    q.idx[6] = (vy && vz) ? b + sz + sy : -1;
+    q.idx[7] = (vx && vy && vz) ? b + sz + sy + 1 : -1;
+  } else {
+    const bool vx[2] = {x0 >= 0 && x0 < W, x0 + 1 >= 0 && x0 + 1 < W};
+    const bool vy[2] = {y0 >= 0 && y0 < H, y0 + 1 >= 0 && y0 + 1 < H};
+    const bool vz[2] = {z0 >= 0 && z0 < D, z0 + 1 >= 0 && z0 + 1 < D};
+    q.allv = true;
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const bool v = vx[c & 1] && vy[(c >> 1) & 1] && vz[(c >> 2) & 1];
-    q.idx[c] = v ? b + (c & 1) + ((c >> 1) & 1) * sy + ((c >> 2) & 1) * sz : -1;
-    q.allv = q.allv && v;
+    for (int c = 0; c < 8; ++c) {
+      const bool v = vx[c & 1] && vy[(c >> 1) & 1] && vz[(c >> 2) & 1];
+      q.idx[c] = v ? b + (c & 1) + ((c >> 1) & 1) * sy + ((c >> 2) & 1) * sz : -1;
+      q.allv = q.allv && v;
+    }
   }
   const float gx = 1.f - q.fx, gy = 1.f - q.fy, gz = 1.f - q.fz;
   const float w00 = gx * gy, w10 = q.fx * gy, w01 = gx * q.fy, w11 = q.fx * q.fy;
@@ -257,11 +246,36 @@ __device__ __forceinline__ bool tri_any(const Tri& q) {
   for (int c = 0; c < 8; ++c) v = v || q.idx[c] >= 0;
   return v;
 }
+// the voxel cell of a sample as one integer: lanes with equal keys share their eight corners (a cell with any corner inside
+// the grid has x0 in [-1, W-1], so with the +1s the key is unique among the cells that matter)
+__device__ __forceinline__ int tri_cell_key(const Tri& q, int H, int W) {
+  return ((q.z0 + 1) * (H + 1) + (q.y0 + 1)) * (W + 1) + (q.x0 + 1);
+}
+
+// trilinear backward with respect to the position (utils.h:619-770): corner_dot(c) = <value at corner c, gradient of the
+// sample>, asked for the corners that exist -> gradient in box coordinates.  (A callable, not an array of eight: with the
+// dot products computed ahead of the corner guard march_bwd took 11.9 instead of 10.8 ms at the config-5 benchmark.)
+template <class CornerDot>
+__device__ __forceinline__ V3 tri_pos_grad(const Tri& q, int D, int H, int W, CornerDot&& corner_dot) {
+  float gix = 0.f, giy = 0.f, giz = 0.f;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    if (q.idx[c] >= 0) {
+      const float dp = corner_dot(c);
+      const int dx = c & 1, dy = (c >> 1) & 1, dz = (c >> 2) & 1;
+      const float wx = dx ? q.fx : 1.f - q.fx, wy = dy ? q.fy : 1.f - q.fy, wz = dz ? q.fz : 1.f - q.fz;
+      gix += (dx ? dp : -dp) * wy * wz;
+      giy += (dy ? dp : -dp) * wx * wz;
+      giz += (dz ? dp : -dp) * wx * wy;
+    }
+  }
+  return v3(gix * 0.5f * (float)(W - 1), giy * 0.5f * (float)(H - 1), giz * 0.5f * (float)(D - 1));
+}
 
 // warped sample position y1 = trilinear(warp field of the box [WD,WH,WW,3], y0) for y0 strictly inside the box
 // (primsampler.h:53-56)
 __device__ __forceinline__ V3 warp_sample(const float* __restrict__ wp, int WD, int WH, int WW, V3 y0, Tri& qw) {
-  tri_setup(qw, WD, WH, WW, y0);
+  tri_setup<true>(qw, WD, WH, WW, y0);
   V3 r = v3(0.f, 0.f, 0.f);
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
@@ -393,6 +407,104 @@ __device__ __forceinline__ float fade_pow_m1(float ax, float e, bool e8) {
   return fast_pow(ax, e - 1.f);
 }
 
+// the fade term of a sample at box coordinates y, and the factor of its derivative: d fade / d y = fade * fade_dfactor
+__device__ __forceinline__ float fade_term(V3 y, float fs, float fe) {
+  const bool e8 = fe == 8.f;
+  return __expf(-fs * (fade_pow(fabsf(y.x), fe, e8) + fade_pow(fabsf(y.y), fe, e8) + fade_pow(fabsf(y.z), fe, e8)));
+}
+__device__ __forceinline__ V3 fade_dfactor(V3 y, float fs, float fe) {
+  const bool e8 = fe == 8.f;
+  const float kf = -(fs * fe);
+  return v3(kf * fade_pow_m1(fabsf(y.x), fe, e8) * (y.x > 0.f ? 1.f : -1.f), kf * fade_pow_m1(fabsf(y.y), fe, e8) * (y.y > 0.f ? 1.f : -1.f),
+            kf * fade_pow_m1(fabsf(y.z), fe, e8) * (y.z > 0.f ? 1.f : -1.f));
+}
+
+// what ray image n reads of the primitive set it belongs to (`group` consecutive images share one; the backward is only
+// launched with group 1)
+struct ImageBase {
+  size_t box0, vox;  // first box of the set among all N/group x K boxes; voxels of one box's template
+  const float* primpos; const float* primrot; const float* primscale; const float* nodeaabb;
+};
+__device__ __forceinline__ ImageBase image_base(const MarchArgs& a, int n) {
+  const int pn = n / a.group;
+  const size_t box0 = (size_t)pn * a.K;
+  return ImageBase{box0, (size_t)a.TD * a.TH * a.TW, a.primpos + box0 * 3, a.primrot + box0 * 9, a.primscale + box0 * 3,
+                   a.nodeaabb + (size_t)pn * (2 * a.K - 1) * 6};
+}
+// box `box`'s field in a [boxes,WD,WH,WW,3] tensor (the warp fields and their gradient)
+template <class T>
+__device__ __forceinline__ T* warp_field(T* base, const MarchArgs& a, size_t box) {
+  return base + box * (size_t)a.WD * a.WH * a.WW * 3;
+}
+
+// the template's cell `q` of a sample at y0: that of y0 itself, or (WARP) of its image under the box's warp field, whose own
+// cell at y0 goes to `qw`.  Every lane gets a `q` (plain arithmetic; only lanes with `ev` use theirs).
+template <bool WARP>
+__device__ __forceinline__ void sample_setup(const MarchArgs& a, size_t box, V3 y0, bool ev, Tri& q, Tri& qw) {
+  if (WARP) {
+    V3 y1 = y0;
+    if (ev) y1 = warp_sample(warp_field(a.warp, a, box), a.WD, a.WH, a.WW, y0, qw);
+    tri_setup<false>(q, a.TD, a.TH, a.TW, y1);
+  } else {
+    tri_setup<true>(q, a.TD, a.TH, a.TW, y0);
+  }
+}
+
+// THE march: forward and backward walk the samples through this one function, so the backward visits exactly what the
+// forward visited.  Calls visit(s, k, xf, y0, ev) for every march step and every box (list slot s, box k, transform xf)
+// whose window contains the step: y0 = the lane's sample in box coordinates, ev = the lane evaluates it.  `sat` is the
+// lane's "ray saturated" flag, set by the visit.
+// The loop condition is !__all(t > rt1 + 1e-5 || done) of subset_kernel.h:81 written so that a lane goes on only while
+// t < rt1 + 1e-5: for finite values the two differ at t == rt1 + 1e-5f alone, where `ev` (which holds the same compare) is
+// false for every lane, so no visit does anything in that extra step; for a NaN t the `!(t > ..)` form never ends, this one
+// does.
+template <class Visit>
+__device__ __forceinline__ void march_walk(const ImageBase& im, float stepsize, Ray& ray, const bool& sat, int num,
+                                           const int* __restrict__ s_list, const unsigned* __restrict__ s_win,
+                                           Visit&& visit) {
+  const int lane = threadIdx.x & 63;
+  int iter = 0;
+  while (gol_ballot(ray.live && ray.t < ray.rt1 + 1e-5f && !sat) != 0ull) {
+    // the boxes whose window contains this iteration, 64 list entries per ballot (lane j tests entry base + j), then a
+    // scalar walk over the set bits in list order: the per-step cost follows the 2-3 boxes the wave is inside, not the
+    // length of the hit list
+    for (int base = 0; base < num; base += 64) {
+      const int s_me = base + lane;
+      unsigned long long active = gol_ballot(s_me < num && window_active(s_win[s_me], iter));
+      while (active) {
+        const int s = base + __builtin_ctzll(active);
+        active &= active - 1;
+        const int e = __builtin_amdgcn_readfirstlane(s_list[s]);  // wave-uniform: the box transform comes through scalar loads
+        const int k = e & kBoxMask;
+        Xform xf;
+        const V3 y0 = xform_fwd(xf, im.primpos, im.primrot, im.primscale, k, ray.pos);
+        // (half_keeps: a lane only evaluates boxes of ITS half's list; below the cap that is implied by valid_pos)
+        const bool ev = ray.live && half_keeps(e, lane) && valid_pos(y0) && !sat && ray.t < ray.rt1 + 1e-5f;
+        visit(s, k, xf, y0, ev);
+      }
+    }
+    ray.t += stepsize;
+    ray.pos = ray.pos + ray.dir * stepsize;
+    ++iter;
+  }
+}
+
+// Groups the lanes with `pred` by `key` (their voxel cell) and calls fn(leader, mine) once per group, wave-uniformly:
+// leader = the group's first lane, mine = this lane belongs to it.  The 64 rays of a wave sample only a handful of
+// distinct cells of a box at one step, and every device-scope float atomic is a fabric transaction on MI355X: the
+// callers reduce a group over the wave and issue ONE atomic per (cell, corner, channel) instead of one per lane
+// (mvpraymarch utils.h:83-113 issues one per lane).
+template <class Fn>
+__device__ __forceinline__ void for_each_cell_group(bool pred, int key, Fn&& fn) {
+  unsigned long long todo = gol_ballot(pred);
+  while (todo) {
+    const int leader = __builtin_ctzll(todo);
+    const bool mine = pred && (key == __builtin_amdgcn_readlane(key, leader));
+    todo &= ~gol_ballot(mine);
+    fn(leader, mine);
+  }
+}
+
 template <bool SHADOW, bool WARP>
 __global__ __launch_bounds__(256) void march_fwd_kernel(MarchArgs a, float* __restrict__ rayrgba,
                                                         float* __restrict__ raysat, float* __restrict__ shadow) {
@@ -402,122 +514,83 @@ __global__ __launch_bounds__(256) void march_fwd_kernel(MarchArgs a, float* __re
   const int lane = threadIdx.x & 63;
   Ray ray; float tmin, tmax; size_t r; int wave;
   load_ray(a, n, ray, tmin, tmax, r, wave);
-  const size_t vox = (size_t)a.TD * a.TH * a.TW;
-  const int pn = n / a.group;  // primitive set of this ray image
-  const float* primpos = a.primpos + (size_t)pn * a.K * 3;
-  const float* primrot = a.primrot + (size_t)pn * a.K * 9;
-  const float* primscale = a.primscale + (size_t)pn * a.K * 3;
-  const float4* tplate = reinterpret_cast<const float4*>(a.tplate) + (size_t)pn * a.K * vox;
-  const float* tplate_a = a.tplate + (size_t)pn * a.K * vox;  // alpha-only layout
+  const ImageBase im = image_base(a, n);
+  const size_t vox = im.vox;
+  const float4* tplate = reinterpret_cast<const float4*>(a.tplate) + im.box0 * vox;
+  const float* tplate_a = a.tplate + im.box0 * vox;  // alpha-only layout
   float* shadow_n = SHADOW ? shadow + (size_t)n * a.K * vox * 2 : nullptr;
-  const int num = build_hits(a.K, a.nodeaabb + (size_t)pn * (2 * a.K - 1) * 6, primpos, primrot, primscale, a.stepsize,
-                             tmin, tmax, ray, s_list[wave], s_win[wave]);
+  const int num = build_hits(a.K, im.nodeaabb, im.primpos, im.primrot, im.primscale, a.stepsize, tmin, tmax, ray,
+                             s_list[wave], s_win[wave]);
 
   float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f, sat0 = -1.f, sat1 = -1.f, sat2 = -1.f;
   bool sat = false;
-  int iter = 0;
-  // !__all(t > rt1 + 1e-5 || done)   (subset_kernel.h:81)
-  while (gol_ballot(ray.live && !(ray.t > ray.rt1 + 1e-5f || sat)) != 0ull) {
-    // the boxes whose window contains this iteration, 64 list entries per ballot (lane j tests entry base + j), then a
-    // scalar walk over the set bits in list order: the per-step cost follows the 2-3 boxes the wave is inside, not the
-    // length of the hit list
-    for (int base = 0; base < num; base += 64) {
-    const int s_me = base + lane;
-    unsigned long long active = gol_ballot(s_me < num && window_active(s_win[wave][s_me], iter));
-    while (active) {
-      const int s = base + __builtin_ctzll(active);
-      active &= active - 1;
-      const int e = __builtin_amdgcn_readfirstlane(s_list[wave][s]);  // wave-uniform: the box transform comes through scalar loads
-      const int k = e & kBoxMask;
-      Xform xf;
-      const V3 y0 = xform_fwd(xf, primpos, primrot, primscale, k, ray.pos);
-      // (half_keeps: a lane only evaluates boxes of ITS half's list; below the cap that is implied by valid_pos)
-      const bool ev = ray.live && half_keeps(e, lane) && valid_pos(y0) && !sat && ray.t < ray.rt1 + 1e-5f;
-      // shadow splat state of this lane (filled inside the branch, scattered wave-wide after it)
-      int sh_idx[SHADOW ? 8 : 1], sh_key = -1;
-      float sh_w[SHADOW ? 8 : 1], sh_vis = 0.f;
-      Tri q;  // (every lane; only evaluating lanes use theirs)
-      if (WARP) {
-        V3 y1 = y0;
-        Tri qw;
-        if (ev) y1 = warp_sample(a.warp + ((size_t)pn * a.K + k) * (size_t)a.WD * a.WH * a.WW * 3, a.WD, a.WH, a.WW, y0, qw);
-        tri_setup_any(q, a.TD, a.TH, a.TW, y1);
+  march_walk(im, a.stepsize, ray, sat, num, s_list[wave], s_win[wave], [&](int, int k, const Xform&, V3 y0, bool ev) {
+    // shadow splat state of this lane (filled inside the branch, scattered wave-wide after it)
+    int sh_idx[SHADOW ? 8 : 1], sh_key = -1;
+    float sh_w[SHADOW ? 8 : 1], sh_vis = 0.f;
+    Tri q, qw;
+    sample_setup<WARP>(a, im.box0 + k, y0, ev, q, qw);
+    const bool all_corners = gol_ballot(ev && !q.allv) == 0ull;
+    if (ev) {
+      const float fade = fade_term(y0, a.fadescale, a.fadeexp);
+      float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+      if (a.alpha_only) {  // (kernel-uniform) shadow march: 4 bytes per voxel instead of 16
+        const float* tp = tplate_a + (size_t)k * vox;
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+          if (q.idx[c] >= 0) s3 += *gol_at(tp, (unsigned)q.idx[c] * 4u) * q.w[c];
       } else {
-        tri_setup(q, a.TD, a.TH, a.TW, y0);
-      }
-      const bool all_corners = gol_ballot(ev && !q.allv) == 0ull;
-      if (ev) {
-        const bool e8 = a.fadeexp == 8.f;
-        const float fade = __expf(-a.fadescale * (fade_pow(fabsf(y0.x), a.fadeexp, e8) + fade_pow(fabsf(y0.y), a.fadeexp, e8) +
-                                                  fade_pow(fabsf(y0.z), a.fadeexp, e8)));
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        if (a.alpha_only) {  // (kernel-uniform) shadow march: 4 bytes per voxel instead of 16
-          const float* tp = tplate_a + (size_t)k * vox;
+        const float4* tp = tplate + (size_t)k * vox;
+        if (all_corners) {  // (wave-uniform) the common case: eight unguarded loads, no exec-mask regions
 #pragma unroll
-          for (int c = 0; c < 8; ++c)
-            if (q.idx[c] >= 0) s3 += *gol_at(tp, (unsigned)q.idx[c] * 4u) * q.w[c];
+          for (int c = 0; c < 8; ++c) {
+            const float4 v = *gol_at(tp, (unsigned)q.idx[c] * 16u);  // uniform box base + 32-bit byte offset
+            s0 += v.x * q.w[c]; s1 += v.y * q.w[c]; s2 += v.z * q.w[c]; s3 += v.w * q.w[c];
+          }
         } else {
-          const float4* tp = tplate + (size_t)k * vox;
-          if (all_corners) {  // (wave-uniform) the common case: eight unguarded loads, no exec-mask regions
 #pragma unroll
-            for (int c = 0; c < 8; ++c) {
-              const float4 v = *gol_at(tp, (unsigned)q.idx[c] * 16u);  // uniform box base + 32-bit byte offset
+          for (int c = 0; c < 8; ++c) {
+            if (q.idx[c] >= 0) {
+              const float4 v = *gol_at(tp, (unsigned)q.idx[c] * 16u);
               s0 += v.x * q.w[c]; s1 += v.y * q.w[c]; s2 += v.z * q.w[c]; s3 += v.w * q.w[c];
             }
-          } else {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-              if (q.idx[c] >= 0) {
-                const float4 v = *gol_at(tp, (unsigned)q.idx[c] * 16u);
-                s0 += v.x * q.w[c]; s1 += v.y * q.w[c]; s2 += v.z * q.w[c]; s3 += v.w * q.w[c];
-              }
-            }
-          }
-        }
-        s3 *= fade;
-        if (SHADOW && (!WARP || tri_any(q))) {  // (a warped sample outside the template splats nothing: sh_key stays -1)
-          sh_vis = 1.f - acc3;
-          sh_key = ((q.z0 + 1) * (a.TH + 1) + (q.y0 + 1)) * (a.TW + 1) + (q.x0 + 1);
-#pragma unroll
-          for (int c = 0; c < 8; ++c) { sh_idx[c] = q.idx[c]; sh_w[c] = q.w[c]; }
-        }
-        // PrimAccumAdditive::forward_prim (primaccum.h:63-79)
-        const float newalpha = acc3 + s3 * a.stepsize;
-        const float contrib = fminf(newalpha, 1.f) - acc3;
-        acc0 += s0 * contrib; acc1 += s1 * contrib; acc2 += s2 * contrib; acc3 += contrib;
-        if (newalpha >= 1.f) {
-          if (!sat) { sat0 = s0; sat1 = s1; sat2 = s2; }
-          sat = true;
-        }
-      }
-      if (SHADOW) {
-        // PrimSplatterTW (primsplatter.h): (w * visibility, w) into the 8 corner voxels.  Like the template gradient of
-        // the backward: group the wave's lanes by voxel cell, reduce each group, and let lanes 15|31 (corner c) and 47|63
-        // (corner c+1) issue ONE pair of atomics per (cell, corner) -- memory-side float atomics per lane are the cost.
-        float* sp = shadow_n + (size_t)k * vox * 2;
-        unsigned long long todo = gol_ballot(WARP ? (ev && sh_key >= 0) : ev);
-        while (todo) {
-          const int leader = __builtin_ctzll(todo);
-          const int key = __builtin_amdgcn_readlane(sh_key, leader);
-          const bool mine = ev && (sh_key == key);
-          todo &= ~gol_ballot(mine);
-#pragma unroll
-          for (int c = 0; c < 8; c += 2) {
-            const int i0 = __builtin_amdgcn_readlane(sh_idx[c], leader), i1 = __builtin_amdgcn_readlane(sh_idx[c + 1], leader);
-            if (i0 < 0 && i1 < 0) continue;
-            const float w0 = mine ? sh_w[c] : 0.f, w1 = mine ? sh_w[c + 1] : 0.f;
-            const float rs = gol_wave_sum4(w0 * sh_vis, w0, w1 * sh_vis, w1);  // lanes 15, 31 | 47, 63
-            const int j = lane >> 4, idx = j < 2 ? i0 : i1;
-            if ((lane & 15) == 15 && idx >= 0) atomicAdd(sp + (size_t)idx * 2 + (j & 1), rs);
           }
         }
       }
+      s3 *= fade;
+      if (SHADOW && (!WARP || tri_any(q))) {  // (a warped sample outside the template splats nothing: sh_key stays -1)
+        sh_vis = 1.f - acc3;
+        sh_key = tri_cell_key(q, a.TH, a.TW);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) { sh_idx[c] = q.idx[c]; sh_w[c] = q.w[c]; }
+      }
+      // PrimAccumAdditive::forward_prim (primaccum.h:63-79)
+      const float newalpha = acc3 + s3 * a.stepsize;
+      const float contrib = fminf(newalpha, 1.f) - acc3;
+      acc0 += s0 * contrib; acc1 += s1 * contrib; acc2 += s2 * contrib; acc3 += contrib;
+      if (newalpha >= 1.f) {
+        if (!sat) { sat0 = s0; sat1 = s1; sat2 = s2; }
+        sat = true;
+      }
     }
+    if (SHADOW) {
+      // PrimSplatterTW (primsplatter.h): (w * visibility, w) into the 8 corner voxels.  Like the template gradient of
+      // the backward: reduce each cell group, and let lanes 15|31 (corner c) and 47|63 (corner c+1) issue ONE pair of
+      // atomics per (cell, corner) -- memory-side float atomics per lane are the cost.
+      float* sp = shadow_n + (size_t)k * vox * 2;
+      for_each_cell_group(WARP ? (ev && sh_key >= 0) : ev, sh_key, [&](int leader, bool mine) {
+#pragma unroll
+        for (int c = 0; c < 8; c += 2) {
+          const int i0 = __builtin_amdgcn_readlane(sh_idx[c], leader), i1 = __builtin_amdgcn_readlane(sh_idx[c + 1], leader);
+          if (i0 < 0 && i1 < 0) continue;
+          const float w0 = mine ? sh_w[c] : 0.f, w1 = mine ? sh_w[c + 1] : 0.f;
+          const float rs = gol_wave_sum4(w0 * sh_vis, w0, w1 * sh_vis, w1);  // lanes 15, 31 | 47, 63
+          const int j = lane >> 4, idx = j < 2 ? i0 : i1;
+          if ((lane & 15) == 15 && idx >= 0) atomicAdd(sp + (size_t)idx * 2 + (j & 1), rs);
+        }
+      });
     }
-    ray.t += a.stepsize;
-    ray.pos = ray.pos + ray.dir * a.stepsize;
-    ++iter;
-  }
+  });
   if (ray.live && rayrgba) {
     *reinterpret_cast<float4*>(rayrgba + 4 * r) = make_float4(acc0, acc1, acc2, acc3);
     if (raysat) { raysat[3 * r] = sat0; raysat[3 * r + 1] = sat1; raysat[3 * r + 2] = sat2; }
@@ -543,17 +616,15 @@ __global__ __launch_bounds__(256) void march_bwd_kernel(MarchArgs a, const float
   Ray ray; float tmin, tmax; size_t r; int wave;
   load_ray(a, n, ray, tmin, tmax, r, wave);
   for (int i = lane; i < kTgSlots * 16; i += 64) (&s_tg[wave][0][0])[i] = 0.f;
-  const size_t vox = (size_t)a.TD * a.TH * a.TW;
-  const float* primpos = a.primpos + (size_t)n * a.K * 3;
-  const float* primrot = a.primrot + (size_t)n * a.K * 9;
-  const float* primscale = a.primscale + (size_t)n * a.K * 3;
-  const float4* tplate = reinterpret_cast<const float4*>(a.tplate) + (size_t)n * a.K * vox;
-  float* g_tplate = grad_tplate + (size_t)n * a.K * vox * 4;
-  float* g_pos = grad_primpos + (size_t)n * a.K * 3;
-  float* g_rot = grad_primrot + (size_t)n * a.K * 9;
-  float* g_scale = grad_primscale + (size_t)n * a.K * 3;
-  const int num = build_hits(a.K, a.nodeaabb + (size_t)n * (2 * a.K - 1) * 6, primpos, primrot, primscale, a.stepsize,
-                             tmin, tmax, ray, s_list[wave], s_win[wave]);
+  const ImageBase im = image_base(a, n);
+  const size_t vox = im.vox;
+  const float4* tplate = reinterpret_cast<const float4*>(a.tplate) + im.box0 * vox;
+  float* g_tplate = grad_tplate + im.box0 * vox * 4;
+  float* g_pos = grad_primpos + im.box0 * 3;
+  float* g_rot = grad_primrot + im.box0 * 9;
+  float* g_scale = grad_primscale + im.box0 * 3;
+  const int num = build_hits(a.K, im.nodeaabb, im.primpos, im.primrot, im.primscale, a.stepsize, tmin, tmax, ray,
+                             s_list[wave], s_win[wave]);
 
   // PrimAccumAdditive::read (primaccum.h:58-61)
   const float4 dL = ray.live ? *reinterpret_cast<const float4*>(grad_rayrgba + 4 * r) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -561,170 +632,106 @@ __global__ __launch_bounds__(256) void march_bwd_kernel(MarchArgs a, const float
   if (ray.live && raysat_im[3 * r] > -1.f) { rs0 = raysat_im[3 * r]; rs1 = raysat_im[3 * r + 1]; rs2 = raysat_im[3 * r + 2]; rs3 = 1.f; }
   float accw = 0.f;
   bool sat = false;
-  int iter = 0;
-  const float fe = a.fadeexp, fs = a.fadescale;
-  while (gol_ballot(ray.live && ray.t < ray.rt1 + 1e-5f && !sat) != 0ull) {
-    for (int base = 0; base < num; base += 64) {  // (see the forward kernel)
-    const int s_me = base + lane;
-    unsigned long long active = gol_ballot(s_me < num && window_active(s_win[wave][s_me], iter));
-    while (active) {
-      const int s = base + __builtin_ctzll(active);
-      active &= active - 1;
-      const int e = __builtin_amdgcn_readfirstlane(s_list[wave][s]);
-      const int k = e & kBoxMask;
-      Xform xf;
-      const V3 y0 = xform_fwd(xf, primpos, primrot, primscale, k, ray.pos);
-      const bool ev = ray.live && half_keeps(e, lane) && valid_pos(y0) && !sat && ray.t < ray.rt1 + 1e-5f;
-      if (gol_ballot(ev) == 0ull) continue;
-      V3 dLy = v3(0.f, 0.f, 0.f);
-      float sd0 = 0.f, sd1 = 0.f, sd2 = 0.f, sd3 = 0.f;
-      // corner indices / weights of every lane (plain arithmetic; only lanes with `ev` use theirs): kept in `q` for the
-      // scatter below instead of being copied out of the branch
-      Tri q;
-      Tri qw;  // WARP: the warp field's cell at y0
-      bool evs = ev;  // lanes taking part in the template-gradient scatter
+  march_walk(im, a.stepsize, ray, sat, num, s_list[wave], s_win[wave], [&](int s, int k, const Xform& xf, V3 y0, bool ev) {
+    if (gol_ballot(ev) == 0ull) return;
+    V3 dLy = v3(0.f, 0.f, 0.f);
+    float sd0 = 0.f, sd1 = 0.f, sd2 = 0.f, sd3 = 0.f;
+    Tri q, qw;  // kept for the scatter below instead of being copied out of the branch
+    sample_setup<WARP>(a, im.box0 + k, y0, ev, q, qw);
+    // lanes taking part in the template-gradient scatter: a warped sample outside the template has no corner to give a
+    // gradient to
+    const bool evs = WARP ? ev && tri_any(q) : ev;
+    if (ev) {
+      const float fade = fade_term(y0, a.fadescale, a.fadeexp);
+      const float4* tp = tplate + (size_t)k * vox;
+      float4 cv[8];
+      float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        cv[c] = (q.idx[c] >= 0) ? *gol_at(tp, (unsigned)q.idx[c] * 16u) : make_float4(0.f, 0.f, 0.f, 0.f);
+        s0 += cv[c].x * q.w[c]; s1 += cv[c].y * q.w[c]; s2 += cv[c].z * q.w[c]; s3 += cv[c].w * q.w[c];
+      }
+      s3 *= fade;
+      // PrimAccumAdditive::forwardbackward_prim (primaccum.h:81-98)
+      const float al = s3 * a.stepsize;
+      sat = sat || (accw + al >= 1.f);
+      const float weight = sat ? (1.f - accw) : al;
+      float d0 = weight * dL.x, d1 = weight * dL.y, d2 = weight * dL.z;
+      float d3 = sat ? 0.f
+                     : a.stepsize * ((s0 - rs0) * dL.x + (s1 - rs1) * dL.y + (s2 - rs2) * dL.z + (1.f - rs3) * dL.w);
+      accw += weight;
+      // PrimSamplerTW::backward (primsampler.h:70-92)
+      dLy = fade_dfactor(y0, a.fadescale, a.fadeexp) * (s3 * d3);
+      d3 *= fade;
+      // trilinear backward (utils.h:619-770): position gradient here, template scatter below
+      V3 dLy1 = tri_pos_grad(q, a.TD, a.TH, a.TW,
+                             [&](int c) { return cv[c].x * d0 + cv[c].y * d1 + cv[c].z * d2 + cv[c].w * d3; });
       if (WARP) {
-        V3 y1 = y0;
-        if (ev) y1 = warp_sample(a.warp + ((size_t)n * a.K + k) * (size_t)a.WD * a.WH * a.WW * 3, a.WD, a.WH, a.WW, y0, qw);
-        tri_setup_any(q, a.TD, a.TH, a.TW, y1);
-        evs = ev && tri_any(q);  // a warped sample outside the template has no corner to give a gradient to
-      } else {
-        tri_setup(q, a.TD, a.TH, a.TW, y0);
+        // warp sampler backward at y0 (the chain of the reference's PyTorch fixture, mvpraymarch.py:621-626): the field's
+        // gradient (plain per-lane atomics: algo 1 has no caller in the reference's models, it is here for the fixture)
+        // and d y1 / d y0 applied to dLy1
+        const float* wp = warp_field(a.warp, a, im.box0 + k);
+        float* gw = warp_field(grad_warp, a, im.box0 + k);
+        dLy1 = tri_pos_grad(qw, a.WD, a.WH, a.WW, [&](int c) {
+          const float* v = gol_at(wp, (unsigned)qw.idx[c] * 12u);
+          float* g = gol_at(gw, (unsigned)qw.idx[c] * 12u);
+          atomicAdd(g, qw.w[c] * dLy1.x); atomicAdd(g + 1, qw.w[c] * dLy1.y); atomicAdd(g + 2, qw.w[c] * dLy1.z);
+          return v[0] * dLy1.x + v[1] * dLy1.y + v[2] * dLy1.z;
+        });
       }
-      const int cellkey = ((q.z0 + 1) * (a.TH + 1) + (q.y0 + 1)) * (a.TW + 1) + (q.x0 + 1);
-      if (ev) {
-        const float ax = fabsf(y0.x), ay = fabsf(y0.y), az = fabsf(y0.z);
-        const bool e8 = fe == 8.f;
-        const float fade = __expf(-fs * (fade_pow(ax, fe, e8) + fade_pow(ay, fe, e8) + fade_pow(az, fe, e8)));
-        const float4* tp = tplate + (size_t)k * vox;
-        float4 cv[8];
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+      dLy = dLy + dLy1;
+      sd0 = d0; sd1 = d1; sd2 = d2; sd3 = d3;
+    }
+    // Template-gradient scatter: reduce each cell group's 8 corners x 4 channels over the wave (v_permlane swaps)
+    float* gt = g_tplate + (size_t)k * vox * 4;
+    for_each_cell_group(evs, tri_cell_key(q, a.TH, a.TW), [&](int leader, bool mine) {
+      // always reduce (even a one-lane group).  The group's lanes are selected ONCE, on the four sample gradients
+      // (the corner weights stay unmasked), and lanes 15, 31, 47, 63 -- which hold the four channel sums of a corner --
+      // issue that corner's atomics themselves: moving the second corner of a pair to lanes 14, 30, .. so that one
+      // instruction covers both cost six vector instructions per pair for one atomic instruction saved
+      // (profiles/r03g_mvp_bwd_probes.txt: all device atomics of this kernel together are 0.3 of its 11.4 ms).
+      const float m0 = mine ? sd0 : 0.f, m1 = mine ? sd1 : 0.f, m2 = mine ? sd2 : 0.f, m3 = mine ? sd3 : 0.f;
+      // phase 1: the eight corners' reduction chains in ONE basic block (the scheduler interleaves them; with the
+      // atomic's exec-mask region after every corner they ran one after the other, each a ~60-cycle dependent chain)
+      float rc[8];
+      int ic[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          cv[c] = (q.idx[c] >= 0) ? *gol_at(tp, (unsigned)q.idx[c] * 16u) : make_float4(0.f, 0.f, 0.f, 0.f);
-          s0 += cv[c].x * q.w[c]; s1 += cv[c].y * q.w[c]; s2 += cv[c].z * q.w[c]; s3 += cv[c].w * q.w[c];
-        }
-        s3 *= fade;
-        // PrimAccumAdditive::forwardbackward_prim (primaccum.h:81-98)
-        const float al = s3 * a.stepsize;
-        sat = sat || (accw + al >= 1.f);
-        const float weight = sat ? (1.f - accw) : al;
-        float d0 = weight * dL.x, d1 = weight * dL.y, d2 = weight * dL.z;
-        float d3 = sat ? 0.f
-                       : a.stepsize * ((s0 - rs0) * dL.x + (s1 - rs1) * dL.y + (s2 - rs2) * dL.z + (1.f - rs3) * dL.w);
-        accw += weight;
-        // PrimSamplerTW::backward (primsampler.h:70-92)
-        const float kf = -(fs * fe);
-        dLy = v3(kf * fade_pow_m1(ax, fe, e8) * (y0.x > 0.f ? 1.f : -1.f), kf * fade_pow_m1(ay, fe, e8) * (y0.y > 0.f ? 1.f : -1.f),
-                 kf * fade_pow_m1(az, fe, e8) * (y0.z > 0.f ? 1.f : -1.f)) * (s3 * d3);
-        d3 *= fade;
-        // trilinear backward (utils.h:619-770): position gradient here, template scatter below
-        float gix = 0.f, giy = 0.f, giz = 0.f;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          if (q.idx[c] >= 0) {
-            const float dp = cv[c].x * d0 + cv[c].y * d1 + cv[c].z * d2 + cv[c].w * d3;
-            const int dx = c & 1, dy = (c >> 1) & 1, dz = (c >> 2) & 1;
-            const float wx = dx ? q.fx : 1.f - q.fx, wy = dy ? q.fy : 1.f - q.fy, wz = dz ? q.fz : 1.f - q.fz;
-            gix += (dx ? dp : -dp) * wy * wz;
-            giy += (dy ? dp : -dp) * wx * wz;
-            giz += (dz ? dp : -dp) * wx * wy;
-          }
-        }
-        V3 dLy1 = v3(gix * 0.5f * (float)(a.TW - 1), giy * 0.5f * (float)(a.TH - 1), giz * 0.5f * (float)(a.TD - 1));
-        if (WARP) {
-          // warp sampler backward at y0 (the chain of the reference's PyTorch fixture, mvpraymarch.py:621-626): the field's
-          // gradient (plain per-lane atomics: algo 1 has no caller in the reference's models, it is here for the fixture)
-          // and d y1 / d y0 applied to dLy1
-          const float* wp = a.warp + ((size_t)n * a.K + k) * (size_t)a.WD * a.WH * a.WW * 3;
-          float* gw = grad_warp + ((size_t)n * a.K + k) * (size_t)a.WD * a.WH * a.WW * 3;
-          float wix = 0.f, wiy = 0.f, wiz = 0.f;
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            if (qw.idx[c] >= 0) {
-              const float* v = gol_at(wp, (unsigned)qw.idx[c] * 12u);
-              float* g = gol_at(gw, (unsigned)qw.idx[c] * 12u);
-              atomicAdd(g, qw.w[c] * dLy1.x); atomicAdd(g + 1, qw.w[c] * dLy1.y); atomicAdd(g + 2, qw.w[c] * dLy1.z);
-              const float dp = v[0] * dLy1.x + v[1] * dLy1.y + v[2] * dLy1.z;
-              const int dx = c & 1, dy = (c >> 1) & 1, dz = (c >> 2) & 1;
-              const float wx = dx ? qw.fx : 1.f - qw.fx, wy = dy ? qw.fy : 1.f - qw.fy, wz = dz ? qw.fz : 1.f - qw.fz;
-              wix += (dx ? dp : -dp) * wy * wz;
-              wiy += (dy ? dp : -dp) * wx * wz;
-              wiz += (dz ? dp : -dp) * wx * wy;
-            }
-          }
-          dLy1 = v3(wix * 0.5f * (float)(a.WW - 1), wiy * 0.5f * (float)(a.WH - 1), wiz * 0.5f * (float)(a.WD - 1));
-        }
-        dLy = dLy + dLy1;
-        sd0 = d0; sd1 = d1; sd2 = d2; sd3 = d3;
+      for (int c = 0; c < 8; ++c) {
+        ic[c] = __builtin_amdgcn_readlane(q.idx[c], leader);
+        rc[c] = gol_wave_sum4(q.w[c] * m0, q.w[c] * m1, q.w[c] * m2, q.w[c] * m3);   // lanes 15, 31, 47, 63
       }
-      // Template-gradient scatter.  The 64 rays of a wave sample only a handful of distinct voxel cells
-      // of this box at this step, and every device-scope float atomic is a fabric transaction on
-      // MI355X: group the lanes by cell (ballot + readlane), reduce each group's 8 corners x 4
-      // channels over the wave (v_permlane swaps) and issue ONE atomic per (cell, corner, channel)
-      // instead of one per lane (mvpraymarch utils.h:83-113 issues one per lane).
-      {
-        float* gt = g_tplate + (size_t)k * vox * 4;
-        unsigned long long todo = gol_ballot(evs);
-        while (todo) {
-          const int leader = __builtin_ctzll(todo);
-          const int key = __builtin_amdgcn_readlane(cellkey, leader);
-          const bool mine = evs && (cellkey == key);
-          const unsigned long long grp = gol_ballot(mine);
-          todo &= ~grp;
-          // always reduce (even a one-lane group).  The group's lanes are selected ONCE, on the four sample gradients
-          // (the corner weights stay unmasked), and lanes 15, 31, 47, 63 -- which hold the four channel sums of a corner --
-          // issue that corner's atomics themselves: moving the second corner of a pair to lanes 14, 30, .. so that one
-          // instruction covers both cost six vector instructions per pair for one atomic instruction saved
-          // (profiles/r03g_mvp_bwd_probes.txt: all device atomics of this kernel together are 0.3 of its 11.4 ms).
-          const float m0 = mine ? sd0 : 0.f, m1 = mine ? sd1 : 0.f, m2 = mine ? sd2 : 0.f, m3 = mine ? sd3 : 0.f;
-          // phase 1: the eight corners' reduction chains in ONE basic block (the scheduler interleaves them; with the
-          // atomic's exec-mask region after every corner they ran one after the other, each a ~60-cycle dependent chain)
-          float rc[8];
-          int ic[8];
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            ic[c] = __builtin_amdgcn_readlane(q.idx[c], leader);
-            rc[c] = gol_wave_sum4(q.w[c] * m0, q.w[c] * m1, q.w[c] * m2, q.w[c] * m3);   // lanes 15, 31, 47, 63
-          }
-          // phase 2: one exec-mask region, the (wave-uniform) validity of a corner is a scalar branch inside it
-          if ((lane & 15) == 15) {
-            float* gl = gol_at(gt, (unsigned)(lane >> 4) * 4u);
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-              if (ic[c] >= 0) atomicAdd(gol_at(gl, (unsigned)ic[c] * 16u), rc[c]);
-          }
-        }
-      }
-      // PrimTransfSRT::backward (primtransf.h:155-179): 15 wave sums, one atomic each
-      const V3 gs = ev ? xf.rxmt * dLy : v3(0.f, 0.f, 0.f);
-      const V3 d = ev ? dLy * xf.ps : v3(0.f, 0.f, 0.f);
-      const float gp0 = -dot(xf.pr0, d), gp1 = -dot(xf.pr1, d), gp2 = -dot(xf.pr2, d);
-      const float r0 = gol_wave_sum4(gs.x, gs.y, gs.z, gp0);
-      const float r1 = gol_wave_sum4(gp1, gp2, xf.xmt.x * d.x, xf.xmt.x * d.y);
-      const float r2 = gol_wave_sum4(xf.xmt.x * d.z, xf.xmt.y * d.x, xf.xmt.y * d.y, xf.xmt.y * d.z);
-      const float r3 = gol_wave_sum4(xf.xmt.z * d.x, xf.xmt.z * d.y, xf.xmt.z * d.z, 0.f);
+      // phase 2: one exec-mask region, the (wave-uniform) validity of a corner is a scalar branch inside it
       if ((lane & 15) == 15) {
-        const int j = lane >> 4;  // 0..3: which of the four sums this lane holds
-        // r0: scale.x scale.y scale.z pos.x | r1: pos.y pos.z rot[0] rot[1] | r2: rot[2..5] | r3: rot[6..8]
-        if (s < kTgSlots) {  // wave-private LDS slot (in-order LDS ops of one wave: plain read-modify-write)
-          float* t = &s_tg[wave][s][j];
-          t[0] += r0; t[4] += r1; t[8] += r2; t[12] += r3;
-        } else {
-          float* p0 = (j < 3) ? (g_scale + 3 * k + j) : (g_pos + 3 * k);
-          atomicAdd(p0, r0);
-          float* p1 = (j < 2) ? (g_pos + 3 * k + 1 + j) : (g_rot + 9 * k + (j - 2));
-          atomicAdd(p1, r1);
-          atomicAdd(g_rot + 9 * k + 2 + j, r2);
-          if (j < 3) atomicAdd(g_rot + 9 * k + 6 + j, r3);
-        }
+        float* gl = gol_at(gt, (unsigned)(lane >> 4) * 4u);
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+          if (ic[c] >= 0) atomicAdd(gol_at(gl, (unsigned)ic[c] * 16u), rc[c]);
+      }
+    });
+    // PrimTransfSRT::backward (primtransf.h:155-179): 15 wave sums, one atomic each
+    const V3 gs = ev ? xf.rxmt * dLy : v3(0.f, 0.f, 0.f);
+    const V3 d = ev ? dLy * xf.ps : v3(0.f, 0.f, 0.f);
+    const float gp0 = -dot(xf.pr0, d), gp1 = -dot(xf.pr1, d), gp2 = -dot(xf.pr2, d);
+    const float r0 = gol_wave_sum4(gs.x, gs.y, gs.z, gp0);
+    const float r1 = gol_wave_sum4(gp1, gp2, xf.xmt.x * d.x, xf.xmt.x * d.y);
+    const float r2 = gol_wave_sum4(xf.xmt.x * d.z, xf.xmt.y * d.x, xf.xmt.y * d.y, xf.xmt.y * d.z);
+    const float r3 = gol_wave_sum4(xf.xmt.z * d.x, xf.xmt.z * d.y, xf.xmt.z * d.z, 0.f);
+    if ((lane & 15) == 15) {
+      const int j = lane >> 4;  // 0..3: which of the four sums this lane holds
+      // r0: scale.x scale.y scale.z pos.x | r1: pos.y pos.z rot[0] rot[1] | r2: rot[2..5] | r3: rot[6..8]
+      if (s < kTgSlots) {  // wave-private LDS slot (in-order LDS ops of one wave: plain read-modify-write)
+        float* t = &s_tg[wave][s][j];
+        t[0] += r0; t[4] += r1; t[8] += r2; t[12] += r3;
+      } else {
+        float* p0 = (j < 3) ? (g_scale + 3 * k + j) : (g_pos + 3 * k);
+        atomicAdd(p0, r0);
+        float* p1 = (j < 2) ? (g_pos + 3 * k + 1 + j) : (g_rot + 9 * k + (j - 2));
+        atomicAdd(p1, r1);
+        atomicAdd(g_rot + 9 * k + 2 + j, r2);
+        if (j < 3) atomicAdd(g_rot + 9 * k + 6 + j, r3);
       }
     }
-    }
-    ray.t += a.stepsize;
-    ray.pos = ray.pos + ray.dir * a.stepsize;
-    ++iter;
-  }
+  });
   // flush: 4 boxes per wave-instruction, lane = (box, component); component order = [scale 0-2 | pos 3-5 | rot 6-14 | -]
   __builtin_amdgcn_wave_barrier();
   const int nflush = min(num, kTgSlots);
@@ -741,23 +748,31 @@ __global__ __launch_bounds__(256) void march_bwd_kernel(MarchArgs a, const float
   }
 }
 
-int check_march(int N, int H, int W, int K, int TD, int TH, int TW, float stepsize) {
-  GOL_REQUIRE(N >= 0 && H >= 0 && W >= 0 && K >= 1 && K <= kBoxMask, "bad sizes");
-  GOL_REQUIRE(TD > 0 && TH > 0 && TW > 0, "bad template size");
-  GOL_REQUIRE(stepsize > 0.f, "stepsize must be positive");
-  GOL_REQUIRE(N <= 65535, "N > 65535");
-  return GOL_OK;
+// What the five march entries share: the size checks (`own_size_error` = the entry's own, or null), the eight input
+// pointers, the kernel arguments (group / alpha_only / warp keep their defaults).  Returns whether the entry goes on to
+// launch; if not, `rc` is what it returns: an error named after `entry`, or GOL_OK for an empty launch, which may come
+// with null pointers.
+bool march_ready(const char* entry, const char* own_size_error, int N, int H, int W, int K, int TD, int TH, int TW,
+                 float stepsize, float fadescale, float fadeexp, const float* raypos, const float* raydir,
+                 const float* tminmax, const float* nodeaabb, const float* primpos, const float* primrot,
+                 const float* primscale, const float* tplate, MarchArgs& a, int& rc) {
+  const bool empty = N == 0 || H == 0 || W == 0;
+  const char* err =
+      !(N >= 0 && H >= 0 && W >= 0 && K >= 1 && K <= kBoxMask) ? "bad sizes"
+      : !(TD > 0 && TH > 0 && TW > 0) ? "bad template size"
+      : !(stepsize > 0.f) ? "stepsize must be positive"
+      : !(N <= 65535) ? "N > 65535"
+      : own_size_error ? own_size_error
+      : !(empty || (raypos && raydir && tminmax && nodeaabb && primpos && primrot && primscale && tplate)) ? "null pointer"
+      : nullptr;
+  if (err) gol_set_error("%s: %s", entry, err);
+  rc = err ? GOL_ERR_INVALID_ARG : GOL_OK;
+  a = MarchArgs{N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb,
+                primpos, primrot, primscale, tplate};
+  return !err && !empty;
 }
-
-// what the five march entries share: the kernel arguments (group / alpha_only / warp keep their defaults) and the grid, one
-// 16x16-pixel workgroup (four 8x8 wave footprints) per tile and ray image
-MarchArgs march_args(int N, int H, int W, int K, int TD, int TH, int TW, float stepsize, float fadescale, float fadeexp,
-                     const float* raypos, const float* raydir, const float* tminmax, const float* nodeaabb,
-                     const float* primpos, const float* primrot, const float* primscale, const float* tplate) {
-  return MarchArgs{N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb,
-                   primpos, primrot, primscale, tplate};
-}
-dim3 march_grid(int N, int H, int W) { return dim3(gol_cdiv(W, 16), gol_cdiv(H, 16), N); }
+// one 16x16-pixel workgroup (four 8x8 wave footprints) per tile and ray image
+dim3 march_grid(const MarchArgs& a) { return dim3(gol_cdiv(a.W, 16), gol_cdiv(a.H, 16), a.N); }
 
 }  // namespace
 
@@ -789,16 +804,12 @@ extern "C" int gol_mvp_march_fwd(int N, int H, int W, int K, const float* raypos
                                  const float* primrot, const float* primscale, const float* tplate, int TD, int TH,
                                  int TW, float fadescale, float fadeexp, float* rayrgba, float* raysat, float* shadow,
                                  void* stream) {
-  int rc = check_march(N, H, W, K, TD, TH, TW, stepsize);
-  if (rc != GOL_OK) return rc;
-  if (N == 0 || H == 0 || W == 0) return GOL_OK;
-  GOL_REQUIRE(raypos && raydir && tminmax && nodeaabb && primpos && primrot && primscale && tplate && rayrgba,
-              "null pointer");
-  MarchArgs a = march_args(N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos,
-                           primrot, primscale, tplate);
-  const dim3 grid = march_grid(N, H, W);
-  if (shadow) march_fwd_kernel<true, false><<<grid, 256, 0, (hipStream_t)stream>>>(a, rayrgba, raysat, shadow);
-  else march_fwd_kernel<false, false><<<grid, 256, 0, (hipStream_t)stream>>>(a, rayrgba, raysat, shadow);
+  MarchArgs a; int rc;
+  if (!march_ready(__func__, nullptr, N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax,
+                   nodeaabb, primpos, primrot, primscale, tplate, a, rc)) return rc;
+  GOL_REQUIRE(rayrgba, "null pointer");
+  if (shadow) march_fwd_kernel<true, false><<<march_grid(a), 256, 0, (hipStream_t)stream>>>(a, rayrgba, raysat, shadow);
+  else march_fwd_kernel<false, false><<<march_grid(a), 256, 0, (hipStream_t)stream>>>(a, rayrgba, raysat, shadow);
   GOL_CHECK_LAUNCH();
   return GOL_OK;
 }
@@ -808,18 +819,14 @@ extern "C" int gol_mvp_march_warp_fwd(int N, int H, int W, int K, const float* r
                                       const float* primrot, const float* primscale, const float* tplate, int TD, int TH,
                                       int TW, const float* warp, int WD, int WH, int WW, float fadescale, float fadeexp,
                                       float* rayrgba, float* raysat, float* shadow, void* stream) {
-  int rc = check_march(N, H, W, K, TD, TH, TW, stepsize);
-  if (rc != GOL_OK) return rc;
-  GOL_REQUIRE(WD > 0 && WH > 0 && WW > 0, "bad warp field size");
-  if (N == 0 || H == 0 || W == 0) return GOL_OK;
-  GOL_REQUIRE(raypos && raydir && tminmax && nodeaabb && primpos && primrot && primscale && tplate && warp && rayrgba,
-              "null pointer");
-  MarchArgs a = march_args(N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos,
-                           primrot, primscale, tplate);
+  MarchArgs a; int rc;
+  if (!march_ready(__func__, (WD > 0 && WH > 0 && WW > 0) ? nullptr : "bad warp field size", N, H, W, K, TD, TH, TW,
+                   stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, tplate, a,
+                   rc)) return rc;
+  GOL_REQUIRE(warp && rayrgba, "null pointer");
   a.warp = warp; a.WD = WD; a.WH = WH; a.WW = WW;
-  const dim3 grid = march_grid(N, H, W);
-  if (shadow) march_fwd_kernel<true, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, rayrgba, raysat, shadow);
-  else march_fwd_kernel<false, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, rayrgba, raysat, shadow);
+  if (shadow) march_fwd_kernel<true, true><<<march_grid(a), 256, 0, (hipStream_t)stream>>>(a, rayrgba, raysat, shadow);
+  else march_fwd_kernel<false, true><<<march_grid(a), 256, 0, (hipStream_t)stream>>>(a, rayrgba, raysat, shadow);
   GOL_CHECK_LAUNCH();
   return GOL_OK;
 }
@@ -829,17 +836,13 @@ extern "C" int gol_mvp_shadow_march(int N, int group, int H, int W, int K, const
                                     const float* primrot, const float* primscale, const float* tplate, int alpha_only,
                                     int TD, int TH, int TW, float fadescale, float fadeexp, float* rayrgba, float* shadow,
                                     void* stream) {
-  int rc = check_march(N, H, W, K, TD, TH, TW, stepsize);
-  if (rc != GOL_OK) return rc;
-  GOL_REQUIRE(group >= 1 && N % group == 0, "N must be a multiple of group");
-  if (N == 0 || H == 0 || W == 0) return GOL_OK;
-  GOL_REQUIRE(raypos && raydir && tminmax && nodeaabb && primpos && primrot && primscale && tplate && shadow,
-              "null pointer");
-  MarchArgs a = march_args(N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos,
-                           primrot, primscale, tplate);
+  MarchArgs a; int rc;
+  if (!march_ready(__func__, (group >= 1 && N % group == 0) ? nullptr : "N must be a multiple of group", N, H, W, K, TD, TH,
+                   TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, tplate,
+                   a, rc)) return rc;
+  GOL_REQUIRE(shadow, "null pointer");
   a.group = group; a.alpha_only = alpha_only ? 1 : 0;
-  const dim3 grid = march_grid(N, H, W);
-  march_fwd_kernel<true, false><<<grid, 256, 0, (hipStream_t)stream>>>(a, rayrgba, nullptr, shadow);
+  march_fwd_kernel<true, false><<<march_grid(a), 256, 0, (hipStream_t)stream>>>(a, rayrgba, nullptr, shadow);
   GOL_CHECK_LAUNCH();
   return GOL_OK;
 }
@@ -850,16 +853,13 @@ extern "C" int gol_mvp_march_bwd(int N, int H, int W, int K, const float* raypos
                                  int TW, float fadescale, float fadeexp, const float* raysat,
                                  const float* grad_rayrgba, float* grad_primpos, float* grad_primrot,
                                  float* grad_primscale, float* grad_tplate, void* stream) {
-  int rc = check_march(N, H, W, K, TD, TH, TW, stepsize);
-  if (rc != GOL_OK) return rc;
-  if (N == 0 || H == 0 || W == 0) return GOL_OK;
-  GOL_REQUIRE(raypos && raydir && tminmax && nodeaabb && primpos && primrot && primscale && tplate, "null pointer");
+  MarchArgs a; int rc;
+  if (!march_ready(__func__, nullptr, N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax,
+                   nodeaabb, primpos, primrot, primscale, tplate, a, rc)) return rc;
   GOL_REQUIRE(raysat && grad_rayrgba && grad_primpos && grad_primrot && grad_primscale && grad_tplate, "null pointer");
-  MarchArgs a = march_args(N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos,
-                           primrot, primscale, tplate);
-  const dim3 grid = march_grid(N, H, W);
-  march_bwd_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(a, raysat, grad_rayrgba, grad_primpos, grad_primrot,
-                                                                  grad_primscale, grad_tplate, nullptr);
+  march_bwd_kernel<false><<<march_grid(a), 256, 0, (hipStream_t)stream>>>(a, raysat, grad_rayrgba, grad_primpos,
+                                                                          grad_primrot, grad_primscale, grad_tplate,
+                                                                          nullptr);
   GOL_CHECK_LAUNCH();
   return GOL_OK;
 }
@@ -871,19 +871,15 @@ extern "C" int gol_mvp_march_warp_bwd(int N, int H, int W, int K, const float* r
                                       const float* raysat, const float* grad_rayrgba, float* grad_primpos,
                                       float* grad_primrot, float* grad_primscale, float* grad_tplate, float* grad_warp,
                                       void* stream) {
-  int rc = check_march(N, H, W, K, TD, TH, TW, stepsize);
-  if (rc != GOL_OK) return rc;
-  GOL_REQUIRE(WD > 0 && WH > 0 && WW > 0, "bad warp field size");
-  if (N == 0 || H == 0 || W == 0) return GOL_OK;
-  GOL_REQUIRE(raypos && raydir && tminmax && nodeaabb && primpos && primrot && primscale && tplate && warp, "null pointer");
-  GOL_REQUIRE(raysat && grad_rayrgba && grad_primpos && grad_primrot && grad_primscale && grad_tplate && grad_warp,
+  MarchArgs a; int rc;
+  if (!march_ready(__func__, (WD > 0 && WH > 0 && WW > 0) ? nullptr : "bad warp field size", N, H, W, K, TD, TH, TW,
+                   stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, tplate, a,
+                   rc)) return rc;
+  GOL_REQUIRE(warp && raysat && grad_rayrgba && grad_primpos && grad_primrot && grad_primscale && grad_tplate && grad_warp,
               "null pointer");
-  MarchArgs a = march_args(N, H, W, K, TD, TH, TW, stepsize, fadescale, fadeexp, raypos, raydir, tminmax, nodeaabb, primpos,
-                           primrot, primscale, tplate);
   a.warp = warp; a.WD = WD; a.WH = WH; a.WW = WW;
-  const dim3 grid = march_grid(N, H, W);
-  march_bwd_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(a, raysat, grad_rayrgba, grad_primpos, grad_primrot,
-                                                                 grad_primscale, grad_tplate, grad_warp);
+  march_bwd_kernel<true><<<march_grid(a), 256, 0, (hipStream_t)stream>>>(a, raysat, grad_rayrgba, grad_primpos, grad_primrot,
+                                                                         grad_primscale, grad_tplate, grad_warp);
   GOL_CHECK_LAUNCH();
   return GOL_OK;
 }

@@ -50,6 +50,20 @@ def _warp_dims(warp, template):
     return warp.shape[2], warp.shape[3], warp.shape[4]
 
 
+def _march_lead(N, H, W, K, raypos, raydir, stepsize, tminmax, nodeaabb, primpos, primrot, primscale, template, TD, TH, TW):
+    """The 16 leading arguments that gol_mvp_march_fwd / _bwd and their warp twins share."""
+    return [c_int(N), c_int(H), c_int(W), c_int(K), fptr(raypos, "raypos"), fptr(raydir, "raydir"), c_float(stepsize),
+            fptr(tminmax, "tminmax"), fptr(nodeaabb, "nodeaabb"), fptr(primpos, "primpos"), fptr(primrot, "primrot"),
+            fptr(primscale, "primscale"), fptr(template, "template"), c_int(TD), c_int(TH), c_int(TW)]
+
+
+def _warp_args(warp, template):
+    """What the warp entries take after the leading arguments; nothing for the entries without a warp field."""
+    if warp is None:
+        return []
+    return [fptr(warp, "warp"), *(c_int(d) for d in _warp_dims(warp, template))]
+
+
 class _MvpLib:
     """Same entry points as the reference's compiled `mvpraymarchlib`."""
 
@@ -81,21 +95,11 @@ class _MvpLib:
         N, H, W = raypos.shape[:3]
         K, TD, TH, TW = _dims(template)
         _need_gpu(raypos, "raypos")
-        if warp is not None:
-            WD, WH, WW = _warp_dims(warp, template)
-            with _lib.device_guard(raypos.device):
-                _lib.call("gol_mvp_march_warp_fwd", c_int(N), c_int(H), c_int(W), c_int(K), fptr(raypos, "raypos"),
-                          fptr(raydir, "raydir"), c_float(stepsize), fptr(tminmax, "tminmax"), fptr(nodeaabb, "nodeaabb"),
-                          fptr(primpos, "primpos"), fptr(primrot, "primrot"), fptr(primscale, "primscale"),
-                          fptr(template, "template"), c_int(TD), c_int(TH), c_int(TW), fptr(warp, "warp"), c_int(WD),
-                          c_int(WH), c_int(WW), c_float(fadescale), c_float(fadeexp), fptr(rayrgba, "rayrgba"),
-                          fptr(raysat, "raysat"), fptr(shadow, "shadow"), stream_ptr())
-            return []
+        wargs = _warp_args(warp, template)
+        lead = _march_lead(N, H, W, K, raypos, raydir, stepsize, tminmax, nodeaabb, primpos, primrot, primscale, template,
+                           TD, TH, TW)
         with _lib.device_guard(raypos.device):
-            _lib.call("gol_mvp_march_fwd", c_int(N), c_int(H), c_int(W), c_int(K), fptr(raypos, "raypos"),
-                      fptr(raydir, "raydir"), c_float(stepsize), fptr(tminmax, "tminmax"), fptr(nodeaabb, "nodeaabb"),
-                      fptr(primpos, "primpos"), fptr(primrot, "primrot"), fptr(primscale, "primscale"),
-                      fptr(template, "template"), c_int(TD), c_int(TH), c_int(TW), c_float(fadescale),
+            _lib.call("gol_mvp_march_warp_fwd" if wargs else "gol_mvp_march_fwd", *lead, *wargs, c_float(fadescale),
                       c_float(fadeexp), fptr(rayrgba, "rayrgba"), fptr(raysat, "raysat"), fptr(shadow, "shadow"),
                       stream_ptr())
         return []
@@ -112,24 +116,16 @@ class _MvpLib:
         N, H, W = raypos.shape[:3]
         K, TD, TH, TW = _dims(template)
         _need_gpu(raypos, "raypos")
-        if warp is not None:
-            WD, WH, WW = _warp_dims(warp, template)
-            if grad_warp is None or grad_warp.shape != warp.shape:
-                raise RuntimeError("grad_warp must have the shape of warp")
-            with _lib.device_guard(raypos.device):
-                _lib.call("gol_mvp_march_warp_bwd", c_int(N), c_int(H), c_int(W), c_int(K), fptr(raypos), fptr(raydir),
-                          c_float(stepsize), fptr(tminmax), fptr(nodeaabb), fptr(primpos), fptr(primrot),
-                          fptr(primscale), fptr(template), c_int(TD), c_int(TH), c_int(TW), fptr(warp, "warp"),
-                          c_int(WD), c_int(WH), c_int(WW), c_float(fadescale), c_float(fadeexp), fptr(raysat, "raysat"),
-                          fptr(grad_rayrgba, "grad_rayrgba"), fptr(grad_primpos), fptr(grad_primrot),
-                          fptr(grad_primscale), fptr(grad_template), fptr(grad_warp, "grad_warp"), stream_ptr())
-            return []
+        wargs = _warp_args(warp, template)
+        if warp is not None and (grad_warp is None or grad_warp.shape != warp.shape):
+            raise RuntimeError("grad_warp must have the shape of warp")
+        lead = _march_lead(N, H, W, K, raypos, raydir, stepsize, tminmax, nodeaabb, primpos, primrot, primscale, template,
+                           TD, TH, TW)
         with _lib.device_guard(raypos.device):
-            _lib.call("gol_mvp_march_bwd", c_int(N), c_int(H), c_int(W), c_int(K), fptr(raypos), fptr(raydir),
-                      c_float(stepsize), fptr(tminmax), fptr(nodeaabb), fptr(primpos), fptr(primrot), fptr(primscale),
-                      fptr(template), c_int(TD), c_int(TH), c_int(TW), c_float(fadescale), c_float(fadeexp),
-                      fptr(raysat, "raysat"), fptr(grad_rayrgba, "grad_rayrgba"), fptr(grad_primpos),
-                      fptr(grad_primrot), fptr(grad_primscale), fptr(grad_template), stream_ptr())
+            _lib.call("gol_mvp_march_warp_bwd" if wargs else "gol_mvp_march_bwd", *lead, *wargs, c_float(fadescale),
+                      c_float(fadeexp), fptr(raysat, "raysat"), fptr(grad_rayrgba, "grad_rayrgba"), fptr(grad_primpos),
+                      fptr(grad_primrot), fptr(grad_primscale), fptr(grad_template),
+                      *([fptr(grad_warp, "grad_warp")] if wargs else []), stream_ptr())
         return []
 
 
