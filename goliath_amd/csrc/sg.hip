@@ -5,16 +5,9 @@
 // light loop runs on scalar (SGPR) loads while the per-Gaussian data streams through coalesced
 // 12-byte-per-lane vector loads.  HBM-bound for small n_lights (40 B/Gaussian fwd, 56 B bwd),
 // VALU-bound (acos + exp + rsqrt per light) beyond ~8 lights.
-#include "gol_common.h"
+#include "gol_sg_lobe.h"
 
 namespace {
-
-constexpr float kTwoPi = 6.28318530718f;        // sg.cu:18
-constexpr float kInv2Pi = 0.15915494309f;       // sg.cu:19
-constexpr float kSqrt2Pi23 = 3.03352966508f;    // sg.cu:20
-constexpr float kInvSqrt2Pi23 = 0.32964899322f; // sg.cu:21
-
-__device__ __forceinline__ float sqr(float v) { return v * v; }
 
 struct f3 { float x, y, z; };
 __device__ __forceinline__ f3 ld3(const float* p, size_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
@@ -31,10 +24,7 @@ __global__ __launch_bounds__(256) void sg_fwd_kernel(
   const size_t e = (size_t)n * D + d;
   const f3 dir = ld3(lobe_dirs, e);
   const f3 pp = ld3(prim_pts, e);
-  const float sigma = lobe_sigmas[e];
-  const float inv_sigma = 1.f / sigma;
-  // lobe normalisation hoisted out of the light loop (one exact division per Gaussian instead of one per light)
-  const float norm = W_TYPE == 0 ? 1.f / (sigma * kSqrt2Pi23) : (W_TYPE == 2 ? 1.f / (sigma * kTwoPi) : 1.f);
+  const gol_sg::Lobe lobe = gol_sg::lobe_of<W_TYPE>(lobe_sigmas[e]);
   const int nL = n_lights[n];
   const float* lv = light_values + (size_t)n * L * 3;
   const float* lp = light_pts + (size_t)n * L * 3;
@@ -43,16 +33,7 @@ __global__ __launch_bounds__(256) void sg_fwd_kernel(
     const float lx = lp[3 * l] - pp.x, ly = lp[3 * l + 1] - pp.y, lz = lp[3 * l + 2] - pp.z;
     const float rn = rsqrtf(lx * lx + ly * ly + lz * lz);
     const float c = fminf(1.f, fmaxf(-1.f, (lx * dir.x + ly * dir.y + lz * dir.z) * rn));
-    float w;
-    if (W_TYPE == 0) {
-      w = __expf(-0.5f * sqr(acosf(c) * inv_sigma)) * norm;
-    } else if (W_TYPE == 1) {
-      w = __expf(-0.5f * sqr(acosf(c) * inv_sigma));
-    } else if (W_TYPE == 2) {
-      w = __expf((c - 1.f) * inv_sigma) * norm;
-    } else {
-      w = __expf((c - 1.f) * inv_sigma);
-    }
+    const float w = gol_sg::weight<W_TYPE>(lobe, c);
     sx += lv[3 * l] * w; sy += lv[3 * l + 1] * w; sz += lv[3 * l + 2] * w;
   }
   integral[3 * e] = sx; integral[3 * e + 1] = sy; integral[3 * e + 2] = sz;
@@ -72,11 +53,7 @@ __global__ __launch_bounds__(256) void sg_bwd_kernel(
   const f3 gi = live ? ld3(grad_integral, e) : f3{0.f, 0.f, 0.f};
   const f3 dir = ld3(lobe_dirs, e);
   const f3 pp = ld3(prim_pts, e);
-  const float sigma = lobe_sigmas[e];
-  const float s2 = sigma * sigma;
-  // per-Gaussian reciprocals: the light loop multiplies (five exact divisions per light otherwise)
-  const float inv_sigma = 1.f / sigma, inv_s2 = 1.f / s2, inv_s3 = 1.f / (s2 * sigma), inv_s4 = 1.f / (s2 * s2);
-  const float norm0 = 1.f / (sigma * kSqrt2Pi23), norm2 = 1.f / (sigma * kTwoPi);
+  const gol_sg::Lobe lobe = gol_sg::lobe_of<W_TYPE>(lobe_sigmas[e]);
   const int nL = n_lights[n];
   const float* lv = light_values + (size_t)n * L * 3;
   const float* lp = light_pts + (size_t)n * L * 3;
@@ -89,39 +66,14 @@ __global__ __launch_bounds__(256) void sg_bwd_kernel(
     const float cc = fminf(1.f, fmaxf(-1.f, c));
     const float ex0 = lv[3 * l], ex1 = lv[3 * l + 1], ex2 = lv[3 * l + 2];
     const float dw = gi.x * ex0 + gi.y * ex1 + gi.z * ex2;
-    float weight, dc;
-    if (W_TYPE == 0 || W_TYPE == 1) {
-      const float angle = acosf(cc);
-      const float ex = __expf(-0.5f * sqr(angle * inv_sigma));
-      // sg.cu:129,139: d acos/dc = -1/sqrt(1-c^2) inside (-1,1), the constant -20 outside
-      const float dacos = (c > -1.f && c < 1.f) ? -rsqrtf(1.f - c * c) : -20.f;
-      if (W_TYPE == 0) {
-        weight = ex * norm0;
-        gs += dw * ((ex * kInvSqrt2Pi23 * (sqr(angle) - s2)) * inv_s4);
-        dc = dw * -((kInvSqrt2Pi23 * angle * ex) * inv_s3) * dacos;
-      } else {
-        weight = ex;
-        gs += dw * ((ex * sqr(angle)) * inv_s3);
-        dc = dw * -((angle * ex) * inv_s2) * dacos;
-      }
-    } else {
-      const float ex = __expf((cc - 1.f) * inv_sigma);
-      if (W_TYPE == 2) {
-        weight = ex * norm2;
-        gs += dw * ((ex * kInv2Pi * ((1.f - cc) - sigma)) * inv_s3);
-        dc = dw * kInv2Pi * ex * inv_s2;
-      } else {
-        weight = ex;
-        gs += dw * ((ex * (1.f - cc) * inv_s2));
-        dc = dw * ex * inv_sigma;
-      }
-    }
-    gx += dc * lx; gy += dc * ly; gz += dc * lz;
+    const gol_sg::Terms t = gol_sg::terms<W_TYPE>(lobe, c, cc, dw);
+    gs += t.gs;
+    gx += t.dc * lx; gy += t.dc * ly; gz += t.dc * lz;
     if (LIGHT_GRAD) {
       // one atomic per wave per light component instead of one per lane (sg.cu:165-169)
-      float a0 = gol_wave_sum_to_lane63(live ? gi.x * weight : 0.f);
-      float a1 = gol_wave_sum_to_lane63(live ? gi.y * weight : 0.f);
-      float a2 = gol_wave_sum_to_lane63(live ? gi.z * weight : 0.f);
+      float a0 = gol_wave_sum_to_lane63(live ? gi.x * t.weight : 0.f);
+      float a1 = gol_wave_sum_to_lane63(live ? gi.y * t.weight : 0.f);
+      float a2 = gol_wave_sum_to_lane63(live ? gi.z * t.weight : 0.f);
       if ((threadIdx.x & 63) == 63) {
         float* g = grad_light_values + ((size_t)n * L + l) * 3;
         atomicAdd(g + 0, a0); atomicAdd(g + 1, a1); atomicAdd(g + 2, a2);

@@ -14,63 +14,38 @@
 //   * backward never re-reads the 113 SH channels: d(loss)/d(f_vnocond) of an SH channel is just
 //     upstream x light coefficient, so it is write-only (452 B) -- the re-read the PyTorch graph
 //     would do (another 452 B) is gone.  Only the 12 geometry channels + f_vcond are re-read.
-#include <cstring>
-
 #include "gol_project.h"
+#include "gol_sg_lobe.h"
 
 namespace {
 
 constexpr float kPi = 3.14159265358979323846f;
-constexpr float kSqrt2Pi23 = 3.03352966508f;     // sg.cu:20
-constexpr float kInvSqrt2Pi23 = 0.32964899322f;  // sg.cu:21
 constexpr float kNormEps = 1e-12f;               // torch F.normalize default eps
 
+// one 16-byte load of a plane streamed once: non-temporal so the planes do not evict the env-map texels from L2
+__device__ __forceinline__ void ld_plane4(const float* __restrict__ p, float (&x)[4]) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
+  x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
+}
+// The backward keeps its state as [..][V] arrays with V = 1 Gaussian per lane (see the note above shade_bwd_kernel)
 template <int V>
 __device__ __forceinline__ void ldv(const float* __restrict__ p, float (&x)[V]) {
-  if constexpr (V == 4) {
-    // streamed once: non-temporal so the planes do not evict the env-map texels from L2
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
-    x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
-  } else if constexpr (V == 2) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const f2 t = __builtin_nontemporal_load(reinterpret_cast<const f2*>(p));
-    x[0] = t.x; x[1] = t.y;
-  } else {
 #pragma unroll
-    for (int v = 0; v < V; ++v) x[v] = p[v];
-  }
+  for (int v = 0; v < V; ++v) x[v] = p[v];
 }
 template <int V>
 __device__ __forceinline__ void stv(float* __restrict__ p, const float (&x)[V]) {
-  if constexpr (V == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
-  } else {
 #pragma unroll
-    for (int v = 0; v < V; ++v) p[v] = x[v];
-  }
+  for (int v = 0; v < V; ++v) p[v] = x[v];
 }
 // [.,N,K] row-major: the K values of V consecutive Gaussians are V*K contiguous floats
 template <int V, int K>
 __device__ __forceinline__ void ld_aos(const float* __restrict__ base, size_t g0, float (&x)[K][V]) {
   float buf[V * K];
   const float* p = base + g0 * K;
-  if constexpr ((V * K) % 4 == 0 && V == 4) {
 #pragma unroll
-    for (int j = 0; j < V * K / 4; ++j) {
-      const float4 t = reinterpret_cast<const float4*>(p)[j];
-      buf[4 * j] = t.x; buf[4 * j + 1] = t.y; buf[4 * j + 2] = t.z; buf[4 * j + 3] = t.w;
-    }
-  } else if constexpr (V == 2) {
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      const float2 t = reinterpret_cast<const float2*>(p)[j];
-      buf[2 * j] = t.x; buf[2 * j + 1] = t.y;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < V * K; ++j) buf[j] = p[j];
-  }
+  for (int j = 0; j < V * K; ++j) buf[j] = p[j];
 #pragma unroll
   for (int v = 0; v < V; ++v)
 #pragma unroll
@@ -84,17 +59,8 @@ __device__ __forceinline__ void st_aos(float* __restrict__ base, size_t g0, cons
 #pragma unroll
     for (int k = 0; k < K; ++k) buf[v * K + k] = x[k][v];
   float* p = base + g0 * K;
-  if constexpr ((V * K) % 4 == 0 && V == 4) {
 #pragma unroll
-    for (int j = 0; j < V * K / 4; ++j)
-      reinterpret_cast<float4*>(p)[j] = make_float4(buf[4 * j], buf[4 * j + 1], buf[4 * j + 2], buf[4 * j + 3]);
-  } else if constexpr (V == 2) {
-#pragma unroll
-    for (int j = 0; j < K; ++j) reinterpret_cast<float2*>(p)[j] = make_float2(buf[2 * j], buf[2 * j + 1]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < V * K; ++j) p[j] = buf[j];
-  }
+  for (int j = 0; j < V * K; ++j) p[j] = buf[j];
 }
 // optional upstream gradient: NULL pointer = zeros
 template <int V, int K>
@@ -121,58 +87,18 @@ struct Bilinear {
 
 // F.grid_sample(mode=bilinear, padding_mode=border, align_corners=False) of a [3,h,w] image at
 // normalised (u,v) in [-1,1]
-template <bool PACKED>
-__device__ __forceinline__ Bilinear bilinear_border(const float* __restrict__ img, int h, int w, float u, float v) {
-  Bilinear r;
-  float ix = ((u + 1.f) * (float)w - 1.f) * 0.5f, iy = ((v + 1.f) * (float)h - 1.f) * 0.5f;
-  r.mx = (ix > 0.f && ix < (float)(w - 1)) ? 1.f : 0.f;
-  r.my = (iy > 0.f && iy < (float)(h - 1)) ? 1.f : 0.f;
-  ix = fminf(fmaxf(ix, 0.f), (float)(w - 1));
-  iy = fminf(fmaxf(iy, 0.f), (float)(h - 1));
-  const float fx0 = floorf(ix), fy0 = floorf(iy);
-  const int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
-  const float wx1 = ix - fx0, wx0 = 1.f - wx1, wy1 = iy - fy0, wy0 = 1.f - wy1;
-  const bool bx = x1 < w, by = y1 < h;
-  float t00[3], t01[3], t10[3], t11[3];
-  if constexpr (PACKED) {
-    // [h,w,16] FOOTPRINT records: record (y0, x0) holds the four taps of the bilinear footprint whose top-left texel
-    // it is (taps beyond the border already zero), 64 bytes on a 64-byte boundary -- a lookup is ONE sector, whatever
-    // its position.  ([h,w,4] texels cost 2.5 sectors per lookup on average: the footprint spans two rows, and the
-    // lookups of neighbouring Gaussians are unrelated, so nothing of the rest of a sector is ever used.)
-    const float4* q = reinterpret_cast<const float4*>(img) + (size_t)(y0 * w + x0) * 4;
-    const float4 a = q[0], b2 = q[1], c2 = q[2], d2 = q[3];
-    t00[0] = a.x; t00[1] = a.y; t00[2] = a.z; t01[0] = b2.x; t01[1] = b2.y; t01[2] = b2.z;
-    t10[0] = c2.x; t10[1] = c2.y; t10[2] = c2.z; t11[0] = d2.x; t11[1] = d2.y; t11[2] = d2.z;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float* p = img + (size_t)c * h * w;
-      t00[c] = p[y0 * w + x0];
-      t01[c] = bx ? p[y0 * w + x1] : 0.f;
-      t10[c] = by ? p[y1 * w + x0] : 0.f;
-      t11[c] = (bx && by) ? p[y1 * w + x1] : 0.f;
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    r.val[c] = wy0 * (wx0 * t00[c] + wx1 * t01[c]) + wy1 * (wx0 * t10[c] + wx1 * t11[c]);
-    r.d_ix[c] = wy0 * (t01[c] - t00[c]) + wy1 * (t11[c] - t10[c]);
-    r.d_iy[c] = wx0 * (t10[c] - t00[c]) + wx1 * (t11[c] - t01[c]);
-  }
-  return r;
-}
-
 struct EnvSample {
   float val[3];      // lerp of the two mip levels (before clamp(max=1))
   float d_u[3], d_v[3];
 };
 
-// the address half of bilinear_border<true>: which footprint record, with which weights
+// F.grid_sample(mode=bilinear, padding_mode=border, align_corners=False) of a [3,h,w] image at normalised (u,v) in
+// [-1,1].  The coordinate half: integer cell of the top-left texel, tap weights, coordinate-clamp gradient masks
 struct Footprint {
-  const float4* q;         // the [h,w,16] record of the top-left texel
-  float wx1, wy1, mx, my;  // tap weights (wx0 = 1 - wx1, ...), coordinate-clamp gradient masks
+  int x0, y0;
+  float wx1, wy1, mx, my;  // wx0 = 1 - wx1, ...
 };
-__device__ __forceinline__ Footprint footprint_of(const float* __restrict__ img, int h, int w, float u, float v) {
+__device__ __forceinline__ Footprint footprint_of(int h, int w, float u, float v) {
   Footprint f;
   float ix = ((u + 1.f) * (float)w - 1.f) * 0.5f, iy = ((v + 1.f) * (float)h - 1.f) * 0.5f;
   f.mx = (ix > 0.f && ix < (float)(w - 1)) ? 1.f : 0.f;
@@ -181,10 +107,15 @@ __device__ __forceinline__ Footprint footprint_of(const float* __restrict__ img,
   iy = fminf(fmaxf(iy, 0.f), (float)(h - 1));
   const float fx0 = floorf(ix), fy0 = floorf(iy);
   f.wx1 = ix - fx0; f.wy1 = iy - fy0;
-  f.q = reinterpret_cast<const float4*>(img) + (size_t)((int)fy0 * w + (int)fx0) * 4;
+  f.x0 = (int)fx0; f.y0 = (int)fy0;
   return f;
 }
-// ... and the arithmetic half, on the four taps already in registers (same expressions as bilinear_border)
+// the [h,w,16] footprint record of that cell: the four taps of the bilinear footprint whose top-left texel it is (taps
+// beyond the border already zero), 64 bytes on a 64-byte boundary -- a lookup is ONE sector, whatever its position
+__device__ __forceinline__ const float4* record_of(const float* __restrict__ recs, int w, const Footprint& f) {
+  return reinterpret_cast<const float4*>(recs) + (size_t)(f.y0 * w + f.x0) * 4;
+}
+// ... and the arithmetic half, on the four taps already in registers 
 __device__ __forceinline__ Bilinear footprint_eval(const Footprint& f, const float4& a, const float4& b2, const float4& c2,
                                                    const float4& d2) {
   Bilinear r;
@@ -198,6 +129,24 @@ __device__ __forceinline__ Bilinear footprint_eval(const Footprint& f, const flo
     r.d_iy[c] = wx0 * (t10[c] - t00[c]) + wx1 * (t11[c] - t01[c]);
   }
   return r;
+}
+
+// the planar [3,h,w] form of a level (GOLIATH_ENVMAP_RECORDS=0): the same four taps gathered from the three planes
+__device__ __forceinline__ Bilinear planar_lookup(const float* __restrict__ img, int h, int w, float u, float v) {
+  const Footprint f = footprint_of(h, w, u, v);
+  const int x0 = f.x0, y0 = f.y0, x1 = x0 + 1, y1 = y0 + 1;
+  const bool bx = x1 < w, by = y1 < h;
+  float4 t[4] = {};
+  float* tt = &t[0].x;  // the four taps as 16 consecutive floats
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float* p = img + (size_t)c * h * w;
+    tt[c] = p[y0 * w + x0];
+    tt[4 + c] = bx ? p[y0 * w + x1] : 0.f;
+    tt[8 + c] = by ? p[y1 * w + x0] : 0.f;
+    tt[12 + c] = (bx && by) ? p[y1 * w + x1] : 0.f;
+  }
+  return footprint_eval(f, t[0], t[1], t[2], t[3]);
 }
 
 // mipmap_grid_sample (mipmap_sampler.py:13-69): level selection has no gradient.
@@ -229,17 +178,21 @@ __device__ __forceinline__ EnvSample env_lookup(const gol_shade_in& in, int b, f
   Bilinear s0, s1;
   if (packed) {
     // both levels' record addresses first, then the eight 16-byte loads back to back: ONE memory round trip per lookup
-    // instead of two dependent ones (round 6; the two bilinear_border calls each waited for their own four loads)
-    const Footprint f0 = footprint_of(m0 + (size_t)b * 16 * h0 * w0, h0, w0, u, v);
-    const Footprint f1 = footprint_of(m1 + (size_t)b * 16 * h1 * w1, h1, w1, u, v);
-    const float4 a0 = f0.q[0], a1 = f0.q[1], a2 = f0.q[2], a3 = f0.q[3];
-    const float4 b0 = f1.q[0], b1 = f1.q[1], b2 = f1.q[2], b3 = f1.q[3];
+    // instead of two dependent ones (round 6; two whole lookups in a row each waited for their own four loads)
+    const float* r0 = m0 + (size_t)b * 16 * h0 * w0;
+    const Footprint f0 = footprint_of(h0, w0, u, v);
+    const float4* q0 = record_of(r0, w0, f0);
+    const float* r1 = m1 + (size_t)b * 16 * h1 * w1;
+    const Footprint f1 = footprint_of(h1, w1, u, v);
+    const float4* q1 = record_of(r1, w1, f1);
+    const float4 a0 = q0[0], a1 = q0[1], a2 = q0[2], a3 = q0[3];
+    const float4 b0 = q1[0], b1 = q1[1], b2 = q1[2], b3 = q1[3];
     s0 = footprint_eval(f0, a0, a1, a2, a3);
     s1 = footprint_eval(f1, b0, b1, b2, b3);
   } else {
-    s0 = bilinear_border<false>(m0 + (size_t)b * 3 * h0 * w0, h0, w0, u, v);
+    s0 = planar_lookup(m0 + (size_t)b * 3 * h0 * w0, h0, w0, u, v);
     s1 = s0;
-    if (q > 1) s1 = bilinear_border<false>(m1 + (size_t)b * 3 * h1 * w1, h1, w1, u, v);
+    if (q > 1) s1 = planar_lookup(m1 + (size_t)b * 3 * h1 * w1, h1, w1, u, v);
   }
   // the driver's per-frame scale of the whole pyramid: the host float, or -- mips_scale_dev -- a float the frame's own
   // kernels left in device memory (gol_envspin_frame: no host read of it).  One wave-uniform load, issued behind the gathers
@@ -272,6 +225,31 @@ struct Geo {
   float vis, m[3], mn, n[3];                         // m = dnml + nmlbase, mn = |m|
   float dvec[3], dn, view[3], vdn, ref[3];           // dvec = pos - campos, dn = |dvec|
 };
+
+// the 22 planes of one Gaussian: the 12 geometry channels of f_vnocond, f_vcond, the uv position and normal maps
+struct Planes { float g[12], fc[4], pb[3], nb[3]; };
+
+// non-temporal loads: the forward streams the planes once
+__device__ __forceinline__ Planes load_planes(const gol_shade_in& in, int b, int nd, int i) {
+  const int N = in.N;
+  const float* F = in.f_vnocond + (size_t)b * (nd + 12) * N + i;
+  Planes x;
+#pragma unroll
+  for (int j = 0; j < 12; ++j) x.g[j] = __builtin_nontemporal_load(F + (size_t)(nd + j) * N);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) x.fc[j] = __builtin_nontemporal_load(in.f_vcond + ((size_t)b * 4 + j) * N + i);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    x.pb[j] = __builtin_nontemporal_load(in.postex + ((size_t)b * 3 + j) * N + i);
+    x.nb[j] = __builtin_nontemporal_load(in.tn + ((size_t)b * 3 + j) * N + i);
+  }
+  return x;
+}
+
+// primscale = clamp(softplus, min, max) (rgca.py:47)
+__device__ __forceinline__ float clamped_scale(const gol_shade_in& in, float sp) {
+  return fminf(fmaxf(sp, in.primscale_min), in.primscale_max);
+}
 
 __device__ __forceinline__ Geo make_geo(const float (&g)[12], const float (&fc)[4], const float (&pb)[3],
                                         const float (&nb)[3], const float* __restrict__ cam) {
@@ -306,20 +284,32 @@ __device__ __forceinline__ Geo make_geo(const float (&g)[12], const float (&fc)[
   return s;
 }
 
+// the env-map direction lightrot x ref and its equirectangular coordinates (envmap.py:284-292)
+struct EnvDir { float rx, ry, rz, u, v; };
+__device__ __forceinline__ void env_rotate(const float* __restrict__ R, const float (&ref)[3], float& rx, float& ry, float& rz) {
+  rx = R[0] * ref[0] + R[1] * ref[1] + R[2] * ref[2];
+  ry = R[3] * ref[0] + R[4] * ref[1] + R[5] * ref[2];
+  rz = R[6] * ref[0] + R[7] * ref[1] + R[8] * ref[2];
+}
+__device__ __forceinline__ EnvDir env_dir(const float* __restrict__ R, const float (&ref)[3]) {
+  EnvDir d;
+  env_rotate(R, ref, d.rx, d.ry, d.rz);
+  d.u = atan2f(d.rx, d.rz) * (1.f / kPi);
+  // polar angle = acos(r_y) (envmap.py:289) evaluated as atan2(sqrt(r_x^2 + r_z^2), r_y): the same angle for a unit vector,
+  // without acos' loss of the rounding of r_y near the poles (acos'(y) = -1 / sqrt(1 - y^2) amplifies it without bound).
+  // The backward likewise forms d acos(r_y) / d r_y = -1 / sqrt(1 - r_y^2) with 1 - r_y^2 as r_x^2 + r_z^2: the difference
+  // cancels to a few ulps of 1 near the poles, the sum keeps the relative precision of the two small components
+  d.v = 2.f * atan2f(sqrtf(d.rx * d.rx + d.rz * d.rz), d.ry) * (1.f / kPi) - 1.f;
+  return d;
+}
+
 // specular radiance before the spec_vis factor; ENV: min(sample, 1) (rgca.py:556)
 template <bool ENV>
 __device__ __forceinline__ void spec_forward(const gol_shade_in& in, int b, const Geo& s, float (&spec)[3],
                                              EnvSample* keep = nullptr) {
   if constexpr (ENV) {
-    const float* R = in.lightrot + 9 * b;
-    const float rx = R[0] * s.ref[0] + R[1] * s.ref[1] + R[2] * s.ref[2];
-    const float ry = R[3] * s.ref[0] + R[4] * s.ref[1] + R[5] * s.ref[2];
-    const float rz = R[6] * s.ref[0] + R[7] * s.ref[1] + R[8] * s.ref[2];
-    const float u = atan2f(rx, rz) * (1.f / kPi);
-    // polar angle = acos(r_y) (envmap.py:289) evaluated as atan2(sqrt(r_x^2 + r_z^2), r_y): the same angle for a unit vector,
-    // without acos' loss of the rounding of r_y near the poles (acos'(y) = -1 / sqrt(1 - y^2) amplifies it without bound)
-    const float v = 2.f * atan2f(sqrtf(rx * rx + rz * rz), ry) * (1.f / kPi) - 1.f;
-    const EnvSample e = env_lookup(in, b, u, v, 5.f * s.sigma);
+    const EnvDir d = env_dir(in.lightrot + 9 * b, s.ref);
+    const EnvSample e = env_lookup(in, b, d.u, d.v, 5.f * s.sigma);
     if (keep) *keep = e;
 #pragma unroll
     for (int c = 0; c < 3; ++c) spec[c] = fminf(e.val[c], 1.f);
@@ -330,14 +320,13 @@ __device__ __forceinline__ void spec_forward(const gol_shade_in& in, int b, cons
     const int nL = in.n_lights[b];
     const float* lv = in.light_intensity + (size_t)b * in.L * 3;
     const float* lp = in.light_pos + (size_t)b * in.L * 3;
-    const float inv_sigma = 1.f / s.sigma, norm = 1.f / (s.sigma * kSqrt2Pi23);
+    const gol_sg::Lobe lobe = gol_sg::lobe_of<0>(s.sigma);
     spec[0] = spec[1] = spec[2] = 0.f;
     for (int l = 0; l < nL; ++l) {
       const float dx = lp[3 * l] - s.pos[0], dy = lp[3 * l + 1] - s.pos[1], dz = lp[3 * l + 2] - s.pos[2];
       const float r = rsqrtf(dx * dx + dy * dy + dz * dz);
       const float c = fminf(1.f, fmaxf(-1.f, (dx * lx + dy * ly + dz * lz) * r));
-      const float ang = acosf(c) * inv_sigma;
-      const float w = __expf(-0.5f * ang * ang) * norm;
+      const float w = gol_sg::weight<0>(lobe, c);
       spec[0] += lv[3 * l] * w; spec[1] += lv[3 * l + 1] * w; spec[2] += lv[3 * l + 2] * w;
     }
   }
@@ -375,19 +364,11 @@ __global__ __launch_bounds__(256, 4) void shade_fwd_kernel(const gol_shade_in in
   float c_spv[3] = {0.f, 0.f, 0.f}, c_alb[3] = {0.f, 0.f, 0.f};   // carried: spec * vis, albedo
   float c_rec[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};             // carried (PROJ): xy, conic, effective opacity, depth
   if (live) {
-    float g[12], fc[4], pb[3], nb[3];
-#pragma unroll
-    for (int j = 0; j < 12; ++j) g[j] = __builtin_nontemporal_load(Fv + (size_t)(nd + j) * N + i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) fc[j] = __builtin_nontemporal_load(in.f_vcond + ((size_t)b * 4 + j) * N + i);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      pb[j] = __builtin_nontemporal_load(in.postex + ((size_t)b * 3 + j) * N + i);
-      nb[j] = __builtin_nontemporal_load(in.tn + ((size_t)b * 3 + j) * N + i);
-    }
+    const Planes x = load_planes(in, b, nd, i);
+    const float (&fc)[4] = x.fc, (&nb)[3] = x.nb;
 #pragma unroll
     for (int c = 0; c < 3; ++c) c_alb[c] = in.albedo[(size_t)i * 3 + c];
-    const Geo s = make_geo(g, fc, pb, nb, in.campos + 3 * b);
+    const Geo s = make_geo(x.g, x.fc, x.pb, x.nb, in.campos + 3 * b);
     float spec[3];
     EnvSample es;
     spec_forward<ENV>(in, b, s, spec, ENV ? &es : nullptr);
@@ -395,7 +376,7 @@ __global__ __launch_bounds__(256, 4) void shade_fwd_kernel(const gol_shade_in in
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       c_spv[c] = spec[c] * s.vis;
-      o_sc[c] = fminf(fmaxf(s.sp[c], in.primscale_min), in.primscale_max);
+      o_sc[c] = clamped_scale(in, s.sp[c]);
     }
     // [B,N,k] rows: lane i writes k consecutive floats, the wave 64 k of them contiguously
     float* p;
@@ -449,7 +430,7 @@ __global__ __launch_bounds__(256, 4) void shade_fwd_kernel(const gol_shade_in in
   auto plane = [&](int ch, float (&x)[4]) {
     const float* src = Fv + (size_t)ch * N + j0c;
     if (VEC4) {
-      ldv<4>(src, x);
+      ld_plane4(src, x);
     } else {
 #pragma unroll
       for (int v = 0; v < 4; ++v) if (j0 + v < N) x[v] = src[v];
@@ -528,7 +509,9 @@ __global__ __launch_bounds__(256, 4) void shade_fwd_kernel(const gol_shade_in in
 // primscale (which other consumers of those outputs may also feed): gol_project_bwd's 56 B written + 56 B re-read per
 // Gaussian and its launch are gone.
 // (launch bound: 3 waves per SIMD = 168 VGPRs.  The env variant sits at 160-171 depending on unrelated code around it; at
-// 171 the kernel drops to 2 waves per SIMD and runs 10 % longer -- round 6 A/B, 301 -> 332 us per 8 views.)
+// 171 the kernel drops to 2 waves per SIMD and runs 10 % longer -- round 6 A/B, 301 -> 332 us per 8 views.  For the same
+// reason phase 1 keeps its [..][V] arrays with V = 1: rewritten with plain scalars, nothing else changed, <1,0,*,1> needs
+// 24 B of scratch where it needs none today -- compile-only table in profiles/shade_refactor_ab.txt.)
 template <bool ENV, bool RAND, bool VEC4, bool PROJ>
 __global__ __launch_bounds__(256, 3) void shade_bwd_kernel(const gol_shade_in in, const gol_shade_out saved,
                                                         const gol_shade_out_grad up, const gol_shade_in_grad gin,
@@ -604,9 +587,8 @@ __global__ __launch_bounds__(256, 3) void shade_bwd_kernel(const gol_shade_in in
           pu.depth = with_depth ? r2.y : 0.f;
           pu.comp = 0.f;
           const gol_proj::View view = gol_proj::view_of(pj.viewmats, pj.intrins, b, pj.img_h, pj.img_w, 16, pj.clip_thresh);
-          const float sc[3] = {pj.glob_scale * fminf(fmaxf(s.sp[0], in.primscale_min), in.primscale_max),
-                               pj.glob_scale * fminf(fmaxf(s.sp[1], in.primscale_min), in.primscale_max),
-                               pj.glob_scale * fminf(fmaxf(s.sp[2], in.primscale_min), in.primscale_max)};
+          const float sc[3] = {pj.glob_scale * clamped_scale(in, s.sp[0]), pj.glob_scale * clamped_scale(in, s.sp[1]),
+                               pj.glob_scale * clamped_scale(in, s.sp[2])};
           const float X[3] = {pj.conics[3 * g0], pj.conics[3 * g0 + 1], pj.conics[3 * g0 + 2]};
           const gol_proj::ProjGrad pg = gol_proj::project_vjp(s.pos, s.q, sc, pj.glob_scale, view, X, pj.comp[g0], pu, true,
                                                               s.opac, nullptr);
@@ -654,9 +636,8 @@ __global__ __launch_bounds__(256, 3) void shade_bwd_kernel(const gol_shade_in in
       float g_ref[3] = {0.f, 0.f, 0.f}, g_sigma = u_sig[0][v];
       if constexpr (ENV) {
         const float* R = in.lightrot + 9 * b;
-        const float rx = R[0] * s.ref[0] + R[1] * s.ref[1] + R[2] * s.ref[2];
-        const float ry = R[3] * s.ref[0] + R[4] * s.ref[1] + R[5] * s.ref[2];
-        const float rz = R[6] * s.ref[0] + R[7] * s.ref[1] + R[8] * s.ref[2];
+        float rx, ry, rz;  // the direction alone: a struct with the two unused angles cost <1,1,1,0> 12 B of scratch
+        env_rotate(R, s.ref, rx, ry, rz);
         float g_u = 0.f, g_v = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -681,8 +662,7 @@ __global__ __launch_bounds__(256, 3) void shade_bwd_kernel(const gol_shade_in in
         const int nL = in.n_lights[b];
         const float* lv = in.light_intensity + (size_t)b * in.L * 3;
         const float* lp = in.light_pos + (size_t)b * in.L * 3;
-        const float sg = s.sigma, s2 = sg * sg;
-        const float inv_sg = 1.f / sg, inv_s3 = 1.f / (s2 * sg), inv_s4 = 1.f / (s2 * s2);  // per Gaussian, not per light
+        const gol_sg::Lobe lobe = gol_sg::lobe_of<0>(s.sigma);
         float gx = 0.f, gy = 0.f, gz = 0.f, gs = 0.f;
         for (int l = 0; l < nL; ++l) {
           float dx = lp[3 * l] - s.pos[0], dy = lp[3 * l + 1] - s.pos[1], dz = lp[3 * l + 2] - s.pos[2];
@@ -690,12 +670,10 @@ __global__ __launch_bounds__(256, 3) void shade_bwd_kernel(const gol_shade_in in
           dx *= r; dy *= r; dz *= r;
           const float c = dx * lx + dy * ly + dz * lz;
           const float cc = fminf(1.f, fmaxf(-1.f, c));
-          const float angle = acosf(cc);
-          const float ex = __expf(-0.5f * (angle * inv_sg) * (angle * inv_sg));
           const float dw = g_sraw[0] * lv[3 * l] + g_sraw[1] * lv[3 * l + 1] + g_sraw[2] * lv[3 * l + 2];
-          const float dacos = (c > -1.f && c < 1.f) ? -rsqrtf(1.f - c * c) : -20.f;
-          gs += dw * ((ex * kInvSqrt2Pi23 * (angle * angle - s2)) * inv_s4);
-          const float dc = dw * -((kInvSqrt2Pi23 * angle * ex) * inv_s3) * dacos;
+          const gol_sg::Terms t = gol_sg::terms<0>(lobe, c, cc, dw);
+          const float dc = t.dc;
+          gs += t.gs;
           gx += dc * dx; gy += dc * dy; gz += dc * dz;
         }
         g_sigma += gs;
@@ -809,7 +787,6 @@ __global__ __launch_bounds__(256, 3) void shade_bwd_kernel(const gol_shade_in in
   }
 }
 
-// [B,3,h,w] planar -> [B,h,w,16] footprint records (see bilinear_border), one lane per record
 // out[i] = sum over the B views of in[b][i]  (the per-view albedo gradients -> the shared parameter's)
 __global__ __launch_bounds__(256) void sum_views_kernel(int B, size_t M, const float* __restrict__ in, float* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -819,6 +796,7 @@ __global__ __launch_bounds__(256) void sum_views_kernel(int B, size_t M, const f
   out[i] = acc;
 }
 
+// [B,3,h,w] planar -> [B,h,w,16] footprint records (see record_of), one lane per record
 __global__ __launch_bounds__(256) void envmap_pack_kernel(int h, int w, const float* __restrict__ src, float4* __restrict__ dst) {
   const int b = blockIdx.y, hw = h * w;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -869,30 +847,19 @@ extern "C" int gol_envmap_pack(int B, int h, int w, const float* src, float* dst
   return GOL_OK;
 }
 
-// VEC4: the SH planes of a view are 16-byte aligned (N % 4 == 0) -> 16-byte plane loads; otherwise scalar ones
-#define GOL_SHADE_FWD_V(V4, P, ...)                                                              \
-  do {                                                                                           \
-    dim3 grid(gol_cdiv(in->N, 256), in->B);                                                      \
-    if (env && rnd) shade_fwd_kernel<true, true, P, V4><<<grid, 256, 0, s>>>(__VA_ARGS__);       \
-    else if (env) shade_fwd_kernel<true, false, P, V4><<<grid, 256, 0, s>>>(__VA_ARGS__);        \
-    else if (rnd) shade_fwd_kernel<false, true, P, V4><<<grid, 256, 0, s>>>(__VA_ARGS__);        \
-    else shade_fwd_kernel<false, false, P, V4><<<grid, 256, 0, s>>>(__VA_ARGS__);                \
-  } while (0)
-
-#define GOL_SHADE_FWD_DISPATCH(P, ...)                                                           \
-  do {                                                                                           \
-    const bool env = in->n_mips > 0, rnd = in->light_sh_rand != nullptr;                         \
-    if (in->N % 4 == 0) GOL_SHADE_FWD_V(true, P, __VA_ARGS__);                                   \
-    else GOL_SHADE_FWD_V(false, P, __VA_ARGS__);                                                 \
-  } while (0)
-
-#define GOL_SHADE_BWD_CASE(E, R, P)                                                              \
-  do {                                                                                           \
-    if (in->N % 4 == 0) shade_bwd_kernel<E, R, true, P><<<grid, 256, 0, s>>>(*in, *saved, *g, *gin, pj, grad_records, with_depth); \
-    else shade_bwd_kernel<E, R, false, P><<<grid, 256, 0, s>>>(*in, *saved, *g, *gin, pj, grad_records, with_depth); \
-  } while (0)
-
 namespace {
+
+// fn(env, rnd, vec4, proj) as four std::true_type / std::false_type: a launch spells its argument list once.
+// vec4: the SH planes of a view are 16-byte aligned (N % 4 == 0) -> 16-byte plane loads / stores; otherwise scalar ones
+template <typename F>
+inline void with_shade_variant(const gol_shade_in* in, bool proj, F&& fn) {
+  auto pick = [](bool on, auto&& k) { if (on) k(std::true_type()); else k(std::false_type()); };
+  pick(in->n_mips > 0, [&](auto env) {
+    pick(in->light_sh_rand != nullptr, [&](auto rnd) {
+      pick(in->N % 4 == 0, [&](auto vec4) { pick(proj, [&](auto pr) { fn(env, rnd, vec4, pr); }); });
+    });
+  });
+}
 
 int check_proj(const gol_shade_in* in, const gol_shade_proj* pj) {
   GOL_REQUIRE(pj != nullptr, "null gol_shade_proj");
@@ -916,14 +883,12 @@ int shade_fwd_launch(const gol_shade_in* in, const gol_shade_out* out, const gol
               "null output");
   GOL_REQUIRE((in->light_sh_rand == nullptr) || out->color_rand, "color_rand output missing");
   hipStream_t s = (hipStream_t)stream;
-  gol_shade_proj pj;
-  memset(&pj, 0, sizeof(pj));
-  if (proj) {
-    pj = *proj;
-    GOL_SHADE_FWD_DISPATCH(true, *in, *out, pj);
-  } else {
-    GOL_SHADE_FWD_DISPATCH(false, *in, *out, pj);
-  }
+  const dim3 grid(gol_cdiv(in->N, 256), in->B);
+  const gol_shade_proj pj = proj ? *proj : gol_shade_proj{};
+  with_shade_variant(in, proj != nullptr, [&](auto env, auto rnd, auto vec4, auto pr) {
+    shade_fwd_kernel<decltype(env)::value, decltype(rnd)::value, decltype(pr)::value, decltype(vec4)::value>
+        <<<grid, 256, 0, s>>>(*in, *out, pj);
+  });
   GOL_CHECK_LAUNCH();
   return GOL_OK;
 }
@@ -941,22 +906,12 @@ int shade_bwd_launch(const gol_shade_in* in, const gol_shade_out* saved, const g
   GOL_REQUIRE(gin->f_vnocond && gin->f_vcond && gin->postex && gin->tn && gin->albedo_per_view, "null gradient output");
   GOL_REQUIRE(!proj || grad_records, "null gradient records");
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(gol_cdiv(in->N, 256), in->B);
-  const bool env = in->n_mips > 0, rnd = in->light_sh_rand != nullptr;
-  gol_shade_proj pj;
-  memset(&pj, 0, sizeof(pj));
-  if (proj) {
-    pj = *proj;
-    if (env && rnd) GOL_SHADE_BWD_CASE(true, true, true);
-    else if (env) GOL_SHADE_BWD_CASE(true, false, true);
-    else if (rnd) GOL_SHADE_BWD_CASE(false, true, true);
-    else GOL_SHADE_BWD_CASE(false, false, true);
-  } else {
-    if (env && rnd) GOL_SHADE_BWD_CASE(true, true, false);
-    else if (env) GOL_SHADE_BWD_CASE(true, false, false);
-    else if (rnd) GOL_SHADE_BWD_CASE(false, true, false);
-    else GOL_SHADE_BWD_CASE(false, false, false);
-  }
+  const dim3 grid(gol_cdiv(in->N, 256), in->B);
+  const gol_shade_proj pj = proj ? *proj : gol_shade_proj{};
+  with_shade_variant(in, proj != nullptr, [&](auto env, auto rnd, auto vec4, auto pr) {
+    shade_bwd_kernel<decltype(env)::value, decltype(rnd)::value, decltype(vec4)::value, decltype(pr)::value>
+        <<<grid, 256, 0, s>>>(*in, *saved, *g, *gin, pj, grad_records, with_depth);
+  });
   GOL_CHECK_LAUNCH();
   if (gin->albedo) {  // gradient of the albedo shared by the views = sum over B of the per-view gradients
     const size_t M = (size_t)in->N * 3;

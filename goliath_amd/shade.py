@@ -149,8 +149,10 @@ class _Shade(torch.autograd.Function):
         with _lib.device_guard(dev):
             # GOLIATH_ENVMAP_RECORDS=0: gather from the planar [.,3,h,w] levels as given (no footprint records)
             packed = pack_envmap(mips) if mips and os.environ.get("GOLIATH_ENVMAP_RECORDS", "1") != "0" else None
-        sin = _make_in(f_vnocond, f_vcond, postex, tn, albedo, light_sh, light_sh_rand, campos,
-                       light_intensity, light_pos, n_lights, list(mips), lightrot, ncol, nmono, packed, mips_scale)
+        # the tensors of gol_shade_in, in _make_in's order: saved first, so that backward rebuilds the struct from them
+        ins = (f_vnocond, f_vcond, postex, tn, albedo, light_sh, light_sh_rand, campos, light_intensity, light_pos,
+               n_lights)
+        sin = _make_in(*ins, list(mips), lightrot, ncol, nmono, packed, mips_scale)
         sout = ShadeOut()
         for n, t in outs.items():
             setattr(sout, n, _p(t))
@@ -168,10 +170,10 @@ class _Shade(torch.autograd.Function):
         ctx.view_set = view_set
         ctx.cfg = (ncol, nmono, len(mips), rand)
         ctx.mips_scale = mips_scale
+        ctx.n_ins = len(ins)
         ctx.packed = packed  # not an input/output of the node: plain attribute
-        ctx.save_for_backward(f_vnocond, f_vcond, postex, tn, albedo, light_sh, light_sh_rand, campos,
-                              light_intensity, light_pos, n_lights, lightrot, outs["diff_sum"],
-                              outs.get("color_rand"), outs.get("env_saved"), pack, *mips)
+        ctx.save_for_backward(*ins, lightrot, outs["diff_sum"], outs.get("color_rand"), outs.get("env_saved"), pack,
+                              *mips)
         ctx.set_materialize_grads(False)
         names = [n for n in GRAD_FIELDS if n in outs]
         ctx.names = names
@@ -184,14 +186,13 @@ class _Shade(torch.autograd.Function):
     def backward(ctx, *grads):
         ncol, nmono, n_mips, rand = ctx.cfg
         sv = ctx.saved_tensors
-        (f_vnocond, f_vcond, postex, tn, albedo, light_sh, light_sh_rand, campos, light_intensity, light_pos,
-         n_lights, lightrot, diff_sum, color_rand, env_saved, pack) = sv[:16]
-        mips = list(sv[16:])
+        n = ctx.n_ins
+        ins, (lightrot, diff_sum, color_rand, env_saved, pack), mips = sv[:n], sv[n:n + 5], list(sv[n + 5:])
+        f_vnocond, f_vcond, postex, tn, albedo = ins[:5]
         B = f_vnocond.shape[0]
         N = f_vnocond[0, 0].numel()
         dev = f_vnocond.device
-        sin = _make_in(f_vnocond, f_vcond, postex, tn, albedo, light_sh, light_sh_rand, campos,
-                       light_intensity, light_pos, n_lights, mips, lightrot, ncol, nmono, ctx.packed, ctx.mips_scale)
+        sin = _make_in(*ins, mips, lightrot, ncol, nmono, ctx.packed, ctx.mips_scale)
         saved = ShadeOut()
         saved.diff_sum = _p(diff_sum)
         saved.color_rand = _p(color_rand)

@@ -240,3 +240,64 @@ def test_frame_scale_goes_to_the_kernel_and_nothing_is_repacked():
     with pytest.raises(ValueError):      # lightrot must be a rotation (gol_shade_in.lightrot precondition)
         t["lightrot"] = 1.3 * t["lightrot"]
         run([getattr(d, f"mipmap_{i}") for i in range(3)])
+
+
+_LOOKUP_REF = {}
+
+
+def _lookup_case(pyramid, hw):
+    """Inputs and the oracle's outputs / gradients of one (pyramid, map shape) case, computed once for both level forms."""
+    from oracle import shade_ref
+
+    key = (pyramid, hw)
+    if key in _LOOKUP_REF:
+        return _LOOKUP_REF[key]
+    H, W = hw
+    B, N = 2, H * W
+    gen = torch.Generator().manual_seed(71 + 3 * H + len(pyramid))
+    r = lambda *s: torch.randn(*s, generator=gen)
+    inp = dict(f_vnocond=0.3 * r(B, 125, H, W), f_vcond=0.3 * r(B, 4, H, W), postex=60 * r(B, 3, H, W),
+               tn=F.normalize(r(B, 3, H, W), dim=1), albedo=0.2 + 0.6 * torch.rand(1, N, 3, generator=gen))
+    inp["f_vnocond"][:, 113 + 7: 113 + 10] *= 8
+    # sigma = max(0.1 exp(x), 0.01): x over log(0.1) .. log(5) puts the level 5 sigma at 0.05 .. 2.5, every pair of levels
+    inp["f_vnocond"][:, 113 + 11] = -2.3 + 3.9 * torch.rand(B, H, W, generator=gen)
+    light_sh, light_sh_rand = r(B, 3, 81) * 0.3, r(B, 3, 81) * 0.3
+    campos = torch.tensor([[30.0, -40.0, -900.0], [-500.0, 100.0, -700.0]])
+    mips = [torch.rand(B, 3, h, w, generator=gen) * 1.5 for h, w in pyramid]
+    rot = torch.linalg.qr(r(B, 3, 3))[0]
+    cpu = {k: v.clone().requires_grad_(True) for k, v in inp.items()}
+    ref = shade_ref.shade(cpu["f_vnocond"], cpu["f_vcond"], cpu["postex"], cpu["tn"], cpu["albedo"], light_sh, campos,
+                          envmips=mips, lightrot=rot, light_sh_rand=light_sh_rand)
+    ws = {k: torch.randn(ref[k].shape, generator=gen) for k in ref}
+    sum((ref[k] * ws[k]).sum() for k in ref if ref[k].requires_grad).backward()
+    case = dict(inp=inp, light_sh=light_sh, light_sh_rand=light_sh_rand, campos=campos, mips=mips, rot=rot, ws=ws,
+                ref={k: v.detach() for k, v in ref.items()}, grad_keys=[k for k in ref if ref[k].requires_grad],
+                grads={k: v.grad for k, v in cpu.items()})
+    _LOOKUP_REF[key] = case
+    return case
+
+
+@pytest.mark.parametrize("records", [True, False])
+@pytest.mark.parametrize("pyramid", [((2, 4), (1, 2)), ((16, 32), (8, 16), (4, 8))])
+@pytest.mark.parametrize("hw", [(13, 20), (17, 17)])  # N = 260: 16-byte planes, partial last workgroup; 289: scalar planes
+def test_env_lookup_forms_vs_oracle(records, pyramid, hw, monkeypatch):
+    """The env-map lookup from footprint records and from the planar levels (GOLIATH_ENVMAP_RECORDS=0), with the random
+    light (the ENV + RAND kernels), on a pyramid with a 1-row level (every lookup clamps in y) and on a three-level one
+    with the roughness spread over all levels, against the torch oracle on outputs and gradients."""
+    from goliath_amd import shade
+
+    monkeypatch.setenv("GOLIATH_ENVMAP_RECORDS", "1" if records else "0")
+    c = _lookup_case(pyramid, hw)
+    gpu = {k: v.clone().cuda().requires_grad_(True) for k, v in c["inp"].items()}
+    out = shade.shading_tail(gpu["f_vnocond"], gpu["f_vcond"], gpu["postex"], gpu["tn"], gpu["albedo"],
+                             c["light_sh"].cuda(), c["campos"].cuda(), preconv_envmap=[m.cuda() for m in c["mips"]],
+                             lightrot=c["rot"].cuda(), light_sh_rand=c["light_sh_rand"].cuda())
+    for k, ref in c["ref"].items():
+        err = rel_l2(out[k].reshape(ref.shape), ref)
+        print(k, err)
+        assert err < TOL, (k, err)
+    sum((out[k].reshape(c["ref"][k].shape) * c["ws"][k].cuda()).sum() for k in c["grad_keys"]).backward()
+    for k, ref in c["grads"].items():
+        err = rel_l2(gpu[k].grad, ref)
+        print("grad", k, err)
+        assert err < TOL, (k, err)
