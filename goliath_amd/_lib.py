@@ -32,6 +32,7 @@ _SYMBOLS = [
     "gol_imgloss_chunk_elems", "gol_imgloss_fwd", "gol_imgloss_finalize", "gol_imgloss_bwd", "gol_depth_disc_mask",
     "gol_mask_erode", "gol_envbg_blur_taps", "gol_envbg_scratch_floats", "gol_envbg_image", "gol_envbg_compose",
     "gol_sh_norm_constants", "gol_sh_basis_fwd", "gol_light_sh_fwd", "gol_envspin_scratch_floats", "gol_envspin_frame",
+    "gol_mvp_template_fwd", "gol_mvp_template_bwd", "gol_mvp_primtransf_fwd", "gol_mvp_primtransf_bwd",
 ]
 
 

@@ -352,3 +352,21 @@ def patch_hand_teacher(teacher_module=None):
         import ca_code.models.hand_teacher_mvp as teacher_module
     teacher_module.OLATRGBDecoder.forward_rgb = urhand.olat_rgb_decoder_forward_rgb
     return teacher_module
+
+
+def patch_hand_mvp(hand_mvp_module=None, full_template=False):
+    """BASELINE config 5's student as a drop-in: `AutoEncoder.render` (ca_code/models/hand_mvp.py:162-205) assembles the
+    compacted primitive template from the decoder slabs with ONE kernel (gol_mvp_template_fwd / _bwd; no full-K copy, no
+    per-step nonzero, implicit pixel grid) and `GeomDecoder.forward` (:386-444) forms primpos / primrot / primscale with
+    gol_mvp_primtransf_fwd / _bwd (goliath_amd.mvpprims.hand_mvp_render / geom_decoder_forward).  The march itself already
+    runs on the HIP kernels.  preds["primrgba"] -- the full-K template only `HandMVPSummary` reads -- is NOT set unless
+    full_template=True (then it is written from the same loads, at the price of one more template-sized store).  Returns
+    the patched module."""
+    from . import mvpprims
+
+    if hand_mvp_module is None:
+        import ca_code.models.hand_mvp as hand_mvp_module
+    setattr(hand_mvp_module.AutoEncoder, mvpprims.FULL_TEMPLATE_FLAG, bool(full_template))
+    hand_mvp_module.AutoEncoder.render = mvpprims.hand_mvp_render
+    hand_mvp_module.GeomDecoder.forward = mvpprims.geom_decoder_forward
+    return hand_mvp_module

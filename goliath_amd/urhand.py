@@ -24,7 +24,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from . import meshraster, mvp, shadowmap, uvlight
+from . import meshraster, mvp, mvpprims, shadowmap, uvlight
 
 
 def _home(obj):
@@ -196,12 +196,11 @@ def deep_shadow(self, mod, primpos, primrot, primscale, primalpha, valid_prims, 
     """The teacher's deep shadow volumes, hand_teacher_mvp.py:271-358: [B, L, n_prim_y, n_prim_x, 1, Z, Y, X]."""
     B, L = light_pos.shape[:2]
     X, Y, Z = self.primsize
-    K = self.n_prim_x * self.n_prim_y
     with torch.no_grad():
         pts = primpos[:, valid_prims.bool()]                                   # [B, Kv, 3]
-        alpha = primalpha.reshape(B, Z, 1, self.n_prim_y, Y, self.n_prim_x, X)
-        alpha = alpha.permute(0, 3, 5, 1, 4, 6, 2).reshape(B, K, Z, Y, X)       # one channel; valid primitives only
-        alpha = valid_prims[None, :, None, None, None] * alpha
+        # one channel [B, K, Z, Y, X]; the primitives outside valid_prims (a 0 / 1 mask) are written as zeros
+        alpha = mvpprims.assemble_template(None, primalpha.reshape(B, Z, self.n_prim_y * Y, self.n_prim_x * X), self.primsize,
+                                           valid_prims=valid_prims, compact=False)
         centre = (pts.max(1)[0] + pts.min(1)[0]) / 2
         centre = centre[:, None].expand(-1, L, -1).reshape(-1, 3)
         lpos = light_pos.reshape(-1, 3).clone()

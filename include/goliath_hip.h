@@ -940,6 +940,48 @@ int gol_envspin_frame(int B, int H, int W, const float* image, const float* rot,
                       float perc90, double env_scale, float* scratch, float* envbg, float* envmap, float* light_intensity,
                       float* norm_scale, float* mip_scale, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Primitive assembly of the MVP hand model (csrc/mvpprims.hip): what hand_mvp.AutoEncoder does between its decoders and
+ * the ray march.
+ * gol_mvp_template_fwd / _bwd replace ca_code/models/hand_mvp.py:171-185 (cat, view, permute(0,3,5,1,4,6,2), reshape of
+ *   the texture slabs) together with the valid_prims selection of ca_code/utils/render_raymarcher.py:41-47
+ *   (template[:, valid_prims].contiguous(), a nonzero with a host sync) and, for the teacher, the alpha-only rearrangement
+ *   and valid_prims * primalpha masking of ca_code/models/hand_teacher_mvp.py:305-311.
+ *     rgb[B,TD,3,Sy,Sx] (NULL: one-channel template) alpha[B,TD,1,Sy,Sx]   Sy = ny TH, Sx = nx TW, K = ny nx; only 4-byte
+ *                                                                          alignment is asked of them
+ *     out[B,Kout,TD,TH,TW,C], C = 4 (rgb + alpha) or 1 (rgb == NULL), 16-byte aligned:
+ *       out[b, slot[k], z, y, x, c] = slab_c[b, z, py TH + y, px TW + x],  k = py nx + px
+ *     slot[K] int32: the primitive's index in `out`, or -1 (outside 0 .. Kout-1) for not written; NULL = identity (then
+ *       Kout == K).  Every index 0 .. Kout-1 must occur once, or `out` keeps unwritten primitives.
+ *     live[K] int32, NULL = all 1: 0 writes zeros into the slot instead of data (the input is then not read).
+ *     out_full[B,K,TD,TH,TW,C], NULL = not wanted: identity slots, all data, from the same loads (preds["primrgba"]).
+ *     act != 0 fuses relu(rgb_scale x + rgb_shift) on the colour planes (hand_mvp.py:472: 25 x + 100) and relu(x) on alpha
+ *       (:434); the product and the sum are rounded separately (PyTorch's composition bit for bit, no FMA: near the
+ *       kink 25 x cancels against 100).  act == 0 is a pure move.
+ *   The input of a primitive that is dropped (slot -1, no out_full) is not read.  _bwd is the transpose: g_out / g_out_full
+ *   (either may be NULL = zero) -> g_rgb (NULL for one channel) and g_alpha, written COMPLETELY (zeros for dropped and dead
+ *   primitives; no zero-filled allocation needed); with act the relu mask is recomputed from rgb / alpha, which may be NULL
+ *   otherwise.  No atomics, no LDS, bitwise repeatable; all offsets 64-bit; Sy Sx < 2^31, B <= 65535.
+ * gol_mvp_primtransf_fwd / _bwd replace hand_mvp.py:410-425 with axisangle_to_matrix (:477-510), one lane per primitive:
+ *     primpos = posbase + rotbase delta_pos, primrot = rotbase A(delta_rvec), primscale = prim_scale delta_scale, with A as
+ *     written there: theta = sqrt(1e-5 + |r|^2), n = r / theta (not unit length), diagonal n_i^2 + (1 - n_i^2) cos theta,
+ *     off-diagonal n_i n_j (1 - cos theta) -+ n_k sin theta.  posbase[B,K,3] and rotbase[B,K,3,3] carry no gradient
+ *     (no_grad in the reference); _bwd gives the three delta gradients analytically (NULL upstream gradient = zero) and is
+ *     finite at delta_rvec = 0.  B K 9 < 2^31.
+ * ---------------------------------------------------------------------------------------- */
+int gol_mvp_template_fwd(int B, int TD, int TH, int TW, int ny, int nx, const float* rgb, const float* alpha,
+                         const int32_t* slot, const int32_t* live, int Kout, int act, float rgb_scale, float rgb_shift,
+                         float* out, float* out_full, void* stream);
+int gol_mvp_template_bwd(int B, int TD, int TH, int TW, int ny, int nx, const float* rgb, const float* alpha,
+                         const int32_t* slot, const int32_t* live, int Kout, int act, float rgb_scale, float rgb_shift,
+                         const float* g_out, const float* g_out_full, float* g_rgb, float* g_alpha, void* stream);
+int gol_mvp_primtransf_fwd(int B, int K, const float* posbase, const float* rotbase, const float* delta_pos,
+                           const float* delta_rvec, const float* delta_scale, float prim_scale, float* primpos,
+                           float* primrot, float* primscale, void* stream);
+int gol_mvp_primtransf_bwd(int B, int K, const float* rotbase, const float* delta_rvec, float prim_scale,
+                           const float* g_primpos, const float* g_primrot, const float* g_primscale, float* g_delta_pos,
+                           float* g_delta_rvec, float* g_delta_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
