@@ -33,6 +33,7 @@ _SYMBOLS = [
     "gol_mask_erode", "gol_envbg_blur_taps", "gol_envbg_scratch_floats", "gol_envbg_image", "gol_envbg_compose",
     "gol_sh_norm_constants", "gol_sh_basis_fwd", "gol_light_sh_fwd", "gol_envspin_scratch_floats", "gol_envspin_frame",
     "gol_mvp_template_fwd", "gol_mvp_template_bwd", "gol_mvp_primtransf_fwd", "gol_mvp_primtransf_bwd",
+    "gol_envprefilter_scratch_floats", "gol_envprefilter_sg",
 ]
 
 

@@ -34,11 +34,15 @@ FLAGS = [
 ]
 
 
-# per-file extra flags (none at present).  Measured and rejected: compiling raster.hip without packed fp32 ops
+# per-file extra flags.  envprefilter.hip: its sample loop calls five double-precision library functions (erfinv, two
+# sincospi, atan2, acos) whose ~150 polynomial coefficients the machine-level loop-invariant code motion would otherwise
+# materialise ahead of the loop and keep live through it: 256 VGPRs + 116 AGPRs, 1 wave per SIMD (2 registers per
+# coefficient; gfx9 VOP3 takes no 64-bit literal).  Without the hoist the coefficients are re-materialised where they are
+# used (two v_mov each): 72 VGPRs, no spill, 7 waves per SIMD (the compiler's resource report).  Measured and rejected: compiling raster.hip without packed fp32 ops
 # ("-Xclang -target-feature -Xclang -packed-fp32-ops") -- the isolated probe prices v_pk_fma_f32 at 2.6x a plain FMA
 # (profiles/r02c_valu_probe.txt), but inside the raster loops both builds take the same time (0.741 / 1.303 ms vs
 # 0.739 / 1.302 ms per 8 views): in situ a packed op costs two plain ones, so only the operation COUNT matters.
-EXTRA_FLAGS = {}
+EXTRA_FLAGS = {"envprefilter.hip": ["-mllvm", "-disable-machine-licm"]}
 
 
 def _sources():

@@ -9,6 +9,8 @@
     dropin.patch_relight_vis()    # optional, with patch_rgca(): run_vis_relight's frames from ONE render + the HIP env background
     dropin.patch_sh()             # optional: sh.dir2sh_torch and (with patch_rgca()) the frame's light SH on ONE HIP launch, no host sync
     dropin.patch_env_driver()     # optional: EnvSpinDecorator.forward's per-frame map rotation, light probe and mip scale on the GPU
+    dropin.patch_env_prefilter()  # optional: envmap.prefilterEnvmapSG (the pyramid of _set_lightmap) on ONE HIP kernel per level
+    dropin.set_environment(decorator, image)   # another environment map for a live EnvSpinDecorator, pyramid built on the GPU
 
 `install()` registers the module names the reference imports for its native code:
     gsplat            project_gaussians, rasterize_gaussians   (ca_code/utils/render_gsplat.py:10-11)
@@ -245,6 +247,66 @@ def patch_env_driver(decorator_module=None):
         forward._goliath_env_driver = True
         cls.forward = forward
     return decorator_module
+
+
+def patch_env_prefilter(envmap_module=None):
+    """Opt in to the fused SG prefilter: `envmap.prefilterEnvmapSG` (ca_code/utils/envmap.py:305-323: num_samples Python
+    iterations of two dozen ATen kernels each) becomes a wrapper that sends CUDA float32 inputs which need no gradient to
+    goliath_amd.envprefilter.prefilter_sg -- two launches -- with a seed drawn from torch's generator (torch.randint on the
+    host: torch.manual_seed makes the result repeatable, as it does the reference's rand_like).  CPU tensors, other dtypes
+    and (grad mode on) inputs that require grad go to the original, kept on the wrapper as `.reference`.  The reference's
+    own EnvSpinDecorator._set_lightmap (light_decorator.py:64-94) then builds its pyramid in three kernel calls, unchanged.
+    Implies none of the other patches; idempotent.  Returns the patched module."""
+    if envmap_module is None:
+        import ca_code.utils.envmap as envmap_module
+    original = envmap_module.prefilterEnvmapSG
+    if not getattr(original, "_goliath_env_prefilter", False):
+        import torch
+
+        from . import envprefilter
+
+        def prefilterEnvmapSG(sigma, v, env_tex, num_samples=1):
+            ok = all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32
+                     and not (torch.is_grad_enabled() and t.requires_grad) for t in (v, env_tex))
+            if not ok:
+                return original(sigma, v, env_tex, num_samples)
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # a host tensor: no device sync
+            return envprefilter.prefilter_sg(sigma, v, env_tex, num_samples, seed=seed)
+
+        prefilterEnvmapSG.reference = original
+        prefilterEnvmapSG._goliath_env_prefilter = True
+        envmap_module.prefilterEnvmapSG = prefilterEnvmapSG
+    return envmap_module
+
+
+def set_environment(decorator, image, num_samples=4096, seed=0):
+    """Give an EnvSpinDecorator another environment map without the reference's loop: `decorator.image` and its `mipmap_i`
+    buffers (light_decorator.py:61-62, :93-94) are REPLACED by `image` [3,H,W] (kept on the device it is given on) and the
+    pyramid goliath_amd.envprefilter.build_pyramid makes of it on the GPU (the image's, else the old pyramid's, else the
+    current one), with the decorator's own sigma_step and miplevel.  New tensors, new addresses: _shared_mipmap and
+    _env_spin_state key their caches on the buffers' address and version and drop their stale copies on the next frame.
+    Returns the decorator."""
+    import torch
+
+    from . import envprefilter
+
+    image = image.detach().to(torch.float32).contiguous()
+    dev = image.device
+    if dev.type != "cuda":           # a host image: build where the pyramid lives, or on the current GPU
+        old = getattr(decorator, "mipmap_0", None)
+        dev = old.device if torch.is_tensor(old) and old.is_cuda else torch.device("cuda")
+    with torch.no_grad():
+        levels = envprefilter.build_pyramid(image.to(dev), sigma_step=decorator.sigma_step, miplevel=decorator.miplevel,
+                                            num_samples=num_samples, seed=seed)
+    # the reference's forward rotates self.image where it lies (light_decorator.py:120): the new one stays on its device
+    decorator.image = image
+    for i, level in enumerate(levels):
+        name = f"mipmap_{i}"
+        if isinstance(decorator, torch.nn.Module) and name not in decorator._buffers:
+            decorator.register_buffer(name, level)
+        else:
+            setattr(decorator, name, level)          # (nn.Module.__setattr__ replaces a registered buffer)
+    return decorator
 
 
 REGULARIZER_LOSSES = ("bound_primscale", "negcolor", "l2_reg", "list_l1_reg", "backlit_reg", "alphaprior", "mask_l1")

@@ -982,6 +982,42 @@ int gol_mvp_primtransf_bwd(int B, int K, const float* rotbase, const float* delt
                            const float* g_primpos, const float* g_primrot, const float* g_primscale, float* g_delta_pos,
                            float* g_delta_rvec, float* g_delta_scale, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The SG prefilter of an environment map, forward only (csrc/envprefilter.hip).  Replaces
+ * ca_code/utils/envmap.py:305-323 prefilterEnvmapSG with what it calls per sample, :251-281 importance_sample_sg and
+ * :284-302 dir2uv / sample_uv (two dozen ATen kernels, four boolean-mask writes and a grid_sample over the whole level per
+ * sample; ca_code/utils/light_decorator.py:64-92 calls it with 4096 samples for each of the three prefiltered levels of the
+ * relight pyramid).  Two launches per call: the repack of the map into 16-byte texels, then one wave per output texel.
+ * gol_envprefilter_sg parameters:
+ *   B, H, W          batch and the size of the direction grid = of the output
+ *   He, We           the size of the map; independent of H, W.  All >= 1
+ *   S                samples per texel (num_samples), >= 1
+ *   sigma            the lobe width, > 0 and finite
+ *   v[B,3,H,W]       the direction n of every output texel (used as given, not normalised: envmap.py:277-280)
+ *   env_tex[B,3,He,We]   the map, planar
+ *   xi[S,B,2,H,W]    the uniform draws, in the order the reference's rand_like(v[:, :2]) returns them in iteration i; or NULL:
+ *                    a Philox-4x32-10 draw with key (seed low, seed high) and counter (g low, g high, y W + x, b),
+ *                    g = sample_offset + i; outputs 0 and 1 of the block, each >> 8 and times 2^-24: [0, 1), never 1.
+ *                    A draw depends on its key and counter only: S samples in one call see the draws of two calls of S / 2
+ *                    with sample_offset 0 and S / 2
+ *   seed, sample_offset   read only when xi is NULL; sample_offset >= 0
+ *   scratch          gol_envprefilter_scratch_floats(B, He, We) floats, 16-byte aligned: the packed map [B,He,We,4]
+ *   out[B,3,H,W]     (sum_i colour_i) / S
+ * Per sample: phi = 2 pi Xi0, theta = sqrt2 sigma erfinv(Xi1 erf(pi / (sqrt2 sigma))), H = (cos phi sin theta,
+ * sin phi sin theta, cos theta); up = (0,0,1) if n_z < 0.999 else (1,0,0), t = normalize(up x n), b = n x t,
+ * d = normalize(t H_x + b H_y + n H_z) (normalize divides by max(norm, 1e-12)); u = atan2(d_x, d_z) / pi,
+ * v = 2 acos(d_y) / pi - 1; grid_sample(bilinear, align_corners=False, padding_mode="border"): ix = ((u + 1) We - 1) / 2
+ * clipped to [0, We - 1] (the u = +-1 seam clamps, it does not wrap).  The pdf the reference computes and drops is not
+ * computed.  One deviation: d_y is clamped to [-1, 1] before acos (the reference gives NaN when normalize lands an ulp
+ * outside).  The frame (t, b) is formed once per texel and erf(pi / (sqrt2 sigma)) once per call, on the host.  Everything
+ * is evaluated in double from the float32 inputs and the mean is rounded once.  Lane l of a texel's wave adds the samples
+ * l, l + 64, ... in ascending order, the 64 partial sums go through one fixed ladder: no atomics, two calls are bitwise
+ * equal, and nothing depends on the grid.  No host sync, no allocation.  B H W < 2^31, 4 B He We < 2^31.
+ * ---------------------------------------------------------------------------------------- */
+int64_t gol_envprefilter_scratch_floats(int B, int He, int We);
+int gol_envprefilter_sg(int B, int H, int W, int He, int We, int S, double sigma, const float* v, const float* env_tex,
+                        const float* xi, int64_t seed, int64_t sample_offset, float* scratch, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
