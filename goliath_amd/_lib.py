@@ -34,6 +34,7 @@ _SYMBOLS = [
     "gol_sh_norm_constants", "gol_sh_basis_fwd", "gol_light_sh_fwd", "gol_envspin_scratch_floats", "gol_envspin_frame",
     "gol_mvp_template_fwd", "gol_mvp_template_bwd", "gol_mvp_primtransf_fwd", "gol_mvp_primtransf_bwd",
     "gol_envprefilter_scratch_floats", "gol_envprefilter_sg",
+    "gol_trunk_conv_fwd", "gol_trunk_conv_bwd_scratch_floats", "gol_trunk_conv_bwd",
 ]
 
 

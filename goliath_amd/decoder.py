@@ -12,6 +12,7 @@ set against the reference class when the reference tree is present).
 smaller values keep the architecture and shrink the slab for tests.
 """
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -94,6 +95,10 @@ class PrimDecoderConvs(nn.Module):
         b = self.base
         z = self.encmod(embs).view(-1, 256, b, b)
         view = self.viewmod(F.normalize(headrel_campos, dim=1))[:, :, None, None].expand(-1, -1, b, b)
+        if os.environ.get("GOLIATH_FUSED_TRUNK", "0") == "1":  # opt-in: hidden layers on gol_trunk_conv_* (trunk.py)
+            from .trunk import run_stack
+
+            return run_stack(self.vnocond_mod[:-1], z), run_stack(self.vcond_mod[:-1], torch.cat([z, view], dim=1))
         return self.vnocond_mod[:-1](z), self.vcond_mod[:-1](torch.cat([z, view], dim=1))
 
     def forward(self, embs, headrel_campos):

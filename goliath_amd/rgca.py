@@ -17,6 +17,7 @@ import os
 from .render_gs import render_batch
 from .shade import shading_tail
 from .tail import fused_tail
+from .trunk import enabled as _fused_trunk, run_stack
 from .uvgeom import fused_topology, uv_geometry
 from .views import ViewSet
 
@@ -211,8 +212,10 @@ def prim_decoder_forward(self, embs: th.Tensor, geom: th.Tensor, headrel_campos:
     view = self.viewmod(F.normalize(headrel_campos, dim=1))[:, :, None, None].expand(-1, -1, 8, 8)
     zv = th.cat([z, view], dim=1)
     fuse = _can_fuse_tail(self)
+    # GOLIATH_FUSED_TRUNK=1: the hidden (conv, LeakyReLU) pairs on gol_trunk_conv_* (goliath_amd/trunk.py); off by default
+    stack = run_stack if _fused_trunk() else (lambda seq, t: seq(t))
     if not fuse:
-        f_vnocond, f_vcond = self.vnocond_mod(z), self.vcond_mod(zv)
+        f_vnocond, f_vcond = stack(self.vnocond_mod, z), stack(self.vcond_mod, zv)
 
     light_sh_rand, light_dir = None, None
     if self.training and (getattr(self, LIGHT_SH_FLAG, False) and self.diff_sh_degree <= 8 and embs.is_cuda
@@ -230,7 +233,7 @@ def prim_decoder_forward(self, embs: th.Tensor, geom: th.Tensor, headrel_campos:
               n_color_sh=self.color_sh_degree, n_diff_sh=self.diff_sh_degree,
               views=getattr(self, "_goliath_view_set", None))
     if fuse:  # the 125-channel activation is never materialised (goliath_amd/tail.py)
-        preds = fused_tail(self.vnocond_mod[-1], self.vcond_mod[-1], self.vnocond_mod[:-1](z), self.vcond_mod[:-1](zv),
+        preds = fused_tail(self.vnocond_mod[-1], self.vcond_mod[-1], stack(self.vnocond_mod[:-1], z), stack(self.vcond_mod[:-1], zv),
                            postex, tn, self.albedo, headrel_light_sh, headrel_campos, **kw)
     else:
         preds = shading_tail(f_vnocond, f_vcond, postex, tn, self.albedo, headrel_light_sh, headrel_campos, **kw)

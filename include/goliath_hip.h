@@ -529,6 +529,29 @@ int gol_tail_conv_bwd(int B, int Ci, int h, int w, int CH, int E, int nd, int wB
 long long gol_tail_conv_bwd_scratch_floats(int B, int h, int w, int CH);
 
 /* ------------------------------------------------------------------------------------------
+ * Hidden decoder layer as one operator (profiles/LOG.md open item 6).  Replaces
+ *   ConvTranspose2dWNUB(Ci -> Co, 4, 2, 1) + LeakyReLU(leak)
+ * (ca_code/nn/layers.py:331-397, weight norm layers.py:157-244, stacked at ca_code/models/rgca.py:408-426,429-454:
+ * one MIOpen transposed convolution, an ATen add of the untied bias and an ATen leaky_relu per layer):
+ *   y[b,co,Y,X] = lrelu( sum_{ci,ky,kx} x[b,ci,iy,ix] w_eff[ci,co,ky,kx] + bias[co,Y,X] ),  Y = 2 iy - 1 + ky, X = 2 ix - 1 + kx
+ *   x [B,Ci,h,w]; w_eff [Ci,Co,4,4] (the weight norm already applied, goliath_amd/tail.py:wn_weight); bias [Co,2h,2w];
+ *   y [B,Co,2h,2w]; leak > 0.  fp32 MFMA, exact fp32.  Nothing but y is written.
+ * Ci must be a multiple of 8 and Co a multiple of 16, otherwise GOL_ERR_UNSUPPORTED; w_eff, w_eff_t, y, g_y and g_bias
+ * must be 16-byte aligned.
+ * bwd forms g_pre = g_y * (y > 0 ? 1 : leak) while loading (any of g_x / g_w / g_bias may be NULL = not wanted, at no cost):
+ *   g_x [B,Ci,h,w] written; needs w_eff_t = w_eff permuted to [Co,4 (kx),Ci,4 (ky)];
+ *   g_w [Ci,Co,4,4] written; needs x and scratch[gol_trunk_conv_bwd_scratch_floats] (per-workgroup partial sums added
+ *       in a fixed order by a second kernel: no float atomics, bitwise reproducible);
+ *   g_bias [Co,2h,2w] written (= sum_b g_pre).
+ * ---------------------------------------------------------------------------------------- */
+int gol_trunk_conv_fwd(int B, int Ci, int Co, int h, int w, float leak, const float* x, const float* w_eff,
+                       const float* bias, float* y, void* stream);
+long long gol_trunk_conv_bwd_scratch_floats(int B, int Ci, int Co, int h, int w);
+int gol_trunk_conv_bwd(int B, int Ci, int Co, int h, int w, float leak, const float* x, const float* w_eff_t,
+                       const float* y, const float* g_y, float* g_x, float* g_w, float* g_bias, float* scratch,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * SSIM image loss ("next" row).  Replaces `ssim` / `_ssim`
  * (ca_code/utils/ssim.py:25-65) as used by rgb_ssim (ca_code/loss/__init__.py:478-494): 11x11 Gaussian
  * window (sigma 1.5, zero padding), C1 = 0.01^2, C2 = 0.03^2, masked mean.
