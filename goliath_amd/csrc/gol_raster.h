@@ -130,6 +130,15 @@ __device__ __forceinline__ Staged stage_entry(const float* __restrict__ records,
   s.mask = wave_mask<PPL>(q0.x, q0.y, cn.x, cn.y, cn.z, q2.z, q2.w, q3.x, q3.y, tile_x0, tile_y0);
   return s;
 }
+// the same with the wave mask the forward of this render left for the entry (its staging ran wave_mask<PPL> on the same
+// tile, record and footprints: the same bits): no reach test, and the record's last 16 bytes are not read
+__device__ __forceinline__ Staged stage_entry_masked(const float* __restrict__ records, size_t g, int mask) {
+  const float4* R = reinterpret_cast<const float4*>(records + g * GOL_SPLAT_RECORD);
+  const float4 q0 = R[0], q1 = R[1], q2 = R[2];
+  Staged s;
+  s.a = q0; s.b = q1; s.c = make_float2(q2.x, q2.y); s.mask = mask;
+  return s;
+}
 
 template <typename V, int P>
 __device__ __forceinline__ bool any_live(const V& live) {
@@ -227,7 +236,7 @@ __device__ __forceinline__ void bwd_recur(const unsigned long long (&mv)[PPL], f
   for (int q = 0; q < PPL; ++q) {
     v[q] = __builtin_amdgcn_inverse_ballot_w64(mv[q]);
     // an entry the pixel did not take enters with alpha = 0: 1 / (1 - 0) = 1 exactly, so T and the running sums pass
-    // through unchanged without further selects
+    // through unchanged without further selects (the composite R of bwd_moments likewise)
     alpha[q] = v[q] ? alpha[q] : 0.f;
   }
   const fvec<PPL> one_m = 1.f - alpha;
@@ -241,16 +250,22 @@ __device__ __forceinline__ void bwd_recur(const unsigned long long (&mv)[PPL], f
 // Backward: v_alpha and gop = e v_alpha with its first two moments in dy, per pixel (lane_sum adds a lane's pixels up).
 // gsplat: v_alpha = sum_c (rgb_c T - buffer_c ra) v_out_c + T_final ra (v_out_alpha - <bg, v_out>) with buffer_c = sum over
 // the Gaussians behind of rgb_c alpha T.  All channels enter through ONE dot product with the upstream gradient, w =
-// <colour, v_out>, so the colour buffers collapse into the running scalar q = sum_behind fac w: v_alpha = T w + ra (tail - q).
+// <colour, v_out>, so the colour buffers collapse into a running scalar q = sum_behind fac w and v_alpha = T w - ra (q - tail),
+// tail = T_final (v_out_alpha - <bg, v_out>).  With T_behind = T (1 - alpha), the transmittance behind the entry,
+// ra (q - tail) = T R for R = (q - tail) / T_behind: R is the back-to-front COMPOSITE of w over what lies behind the entry
+// (background included) and is carried instead of q and tail --
+//   v_alpha = T (w - R),   R <- R (1 - alpha) + alpha w = R + alpha (w - R),   R_start = <bg, v_out> - v_out_alpha
+// -- one running quantity, no T_final factor, no division, and no difference of two sums scaled up by ra when alpha is
+// near its cap.  An entry the pixel did not take has alpha = 0 (bwd_recur) and leaves R as it is.
 // d loss / d sigma per pixel is -opacity * gop; the (wave-uniform) factor -opacity is applied once per Gaussian in
 // the merge step: the lanes reduce the moments of gop itself, whose zeroth moment IS v_opacity
 template <int PPL>
 __device__ __forceinline__ void bwd_moments(const fvec<PPL>& e, const fvec<PPL>& w, const fvec<PPL>& T_cur,
-                                            const fvec<PPL>& ra, const fvec<PPL>& fac, const fvec<PPL>& tail,
-                                            const bool (&v)[PPL], const fvec<PPL>& dy, fvec<PPL>& qsum, fvec<PPL>& gop,
-                                            fvec<PPL>& gy, fvec<PPL>& gyy) {
-  const fvec<PPL> v_alpha = T_cur * w + ra * (tail - qsum);
-  qsum += fac * w;
+                                            const fvec<PPL>& alpha, const bool (&v)[PPL], const fvec<PPL>& dy,
+                                            fvec<PPL>& R, fvec<PPL>& gop, fvec<PPL>& gy, fvec<PPL>& gyy) {
+  const fvec<PPL> d = w - R;
+  const fvec<PPL> v_alpha = T_cur * d;
+  R += alpha * d;
   gop = e * v_alpha;
 #pragma unroll
   for (int q = 0; q < PPL; ++q) gop[q] = v[q] ? gop[q] : 0.f;

@@ -44,7 +44,8 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_fwd_kernel(
     float* __restrict__ out_extra, float* __restrict__ final_Ts, int32_t* __restrict__ final_idx,
     float* __restrict__ out_alpha, float* __restrict__ out_extra_norm, float norm_lo,
     const float* __restrict__ l1_target, const float* __restrict__ l1_mask, int l1_mask_c,
-    uint8_t* __restrict__ l1_sign, float* __restrict__ l1_partial, int n_views, int bg_group, int bg_vec16) {
+    uint8_t* __restrict__ l1_sign, float* __restrict__ l1_partial, int n_views, int bg_group, int bg_vec16,
+    uint8_t* __restrict__ stage_mask) {
   typedef typename Pix<PPL>::fv fv;
   typedef typename Pix<PPL>::iv iv;
   constexpr int NW = Pix<PPL>::kWaves, NT = 64 * NW;
@@ -214,6 +215,11 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_fwd_kernel(
 
   const int32_t* ids = sorted_ids + (size_t)view * capacity;
   const size_t goff = (size_t)view * N;
+  // (optional) the wave mask of every staged entry, one byte at the entry's list index, for the backward of this render: a
+  // batch is staged whole, and a pixel's final_idx lies in a batch that was staged, so every entry the backward can
+  // start from or pass has its byte.  (Two pixels per lane only: the backward's own footprint unless it is forced, and in
+  // the four-wave forward the store costs the <no extra, lazy> instance a wave per SIMD, 64 -> 66 VGPRs.)
+  uint8_t* __restrict__ o_mask = (PPL == 2 && stage_mask) ? stage_mask + (size_t)view * capacity : nullptr;
 
   fv T_cur = 1.f;
   iv cur_idx = 0;
@@ -228,6 +234,7 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_fwd_kernel(
       if (idx < range.y) {
         const Staged st = stage_entry<PPL>(records, goff + (size_t)ids[idx], (float)(tc.tx * 16), (float)(tc.ty * 16));
         s_a[k] = st.a; s_b[k] = st.b; s_c[k] = st.c; s_mask[k] = st.mask;
+        if (PPL == 2 && o_mask) *gol_at(o_mask, (unsigned)idx) = (uint8_t)st.mask;   // consecutive threads, consecutive bytes
       } else {
         s_mask[k] = 0;
       }
@@ -403,7 +410,7 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
     const float* __restrict__ v_out_alpha, float* __restrict__ v_xy, float* __restrict__ v_conic,
     float* __restrict__ v_colors, float* __restrict__ v_extra, float* __restrict__ v_opacity,
     const uint8_t* __restrict__ v_sign, const float* __restrict__ v_sign_mask, int v_sign_mask_c,
-    const float* __restrict__ v_img_scale, float v_img_scale_mul, int n_views) {
+    const float* __restrict__ v_img_scale, float v_img_scale_mul, int n_views, const uint8_t* __restrict__ stage_mask) {
   typedef typename Pix<PPL>::fv fv;
   typedef typename Pix<PPL>::iv iv;
   constexpr int NW = Pix<PPL>::kWaves, NT = 64 * NW;
@@ -469,8 +476,8 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
       if (v_out_alpha) voa[q] = v_out_alpha[p];
     }
   }
-  const fv tail = T_final * (voa - (background[0] * vo0 + background[1] * vo1 + background[2] * vo2));
-  fv qsum = 0.f;  // running sum over the Gaussians behind of fac * <colour, v_out>
+  // composite of <colour, v_out> over what lies behind the current entry: at the start, the background (see bwd_moments)
+  fv R = (background[0] * vo0 + background[1] * vo1 + background[2] * vo2) - voa;
 
   const int wmax = wave_last_entry<PPL>(bin_final);
   if (lane == 0) s_wmax[wave] = wmax;
@@ -490,7 +497,14 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
     const int e = bmax - bb2 * kBatchB - tid;
     return (tid < kBatchB && e >= range.x) ? ids[e] : 0;
   };
-  int gid_next = entry_id(0);
+  // stage_mask (kernel-uniform; NULL = run the reach test here): the wave masks this render's forward staged with the same
+  // footprints, one byte per list entry.  The byte rides the id's prefetch, and staging is three 16-byte loads and no test
+  const uint8_t* __restrict__ i_mask = stage_mask ? stage_mask + (size_t)view * capacity : nullptr;
+  auto entry_mask = [&](int bb2) {
+    const int e = bmax - bb2 * kBatchB - tid;
+    return (i_mask && tid < kBatchB && e >= range.x) ? (int)i_mask[e] : 0;
+  };
+  int gid_next = entry_id(0), mask_next = entry_mask(0);
   // (PACKED) bytes of a gradient record as a value the compiler cannot see through: with the constant, id * 64 + base
   // becomes a 64-bit shift and a 64-bit add per atomic; with an opaque factor it is one v_mad_u64_u32
   unsigned rec_bytes = GOL_GRAD_RECORD * sizeof(float);
@@ -499,17 +513,18 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
     __syncthreads();
     const int batch_end = bmax - bb * kBatchB;
     const int batch_size = min(kBatchB, batch_end + 1 - range.x);
-    const int gid = gid_next;
+    const int gid = gid_next, mask = mask_next;
     if (tid < kBatchB) {
       if (tid < batch_size) {
-        const Staged st = stage_entry<PPL>(records, goff + (size_t)gid, (float)(tc.tx * 16), (float)(tc.ty * 16));
+        const Staged st = i_mask ? stage_entry_masked(records, goff + (size_t)gid, mask)
+                                 : stage_entry<PPL>(records, goff + (size_t)gid, (float)(tc.tx * 16), (float)(tc.ty * 16));
         s_e[tid].a = st.a; s_e[tid].b = st.b; s_e[tid].c = st.c; s_mask[tid] = st.mask;
         s_id[tid] = gid;
       } else {
         s_mask[tid] = 0;
       }
     }
-    if (bb + 1 < n_batches) gid_next = entry_id(bb + 1);
+    if (bb + 1 < n_batches) { gid_next = entry_id(bb + 1); mask_next = entry_mask(bb + 1); }
     (&s_touched[0][0])[tid] = 0;  // NW * kBatchB == blockDim
     __syncthreads();
 
@@ -535,7 +550,7 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
       fv w = b4.z * vo0 + b4.w * vo1 + c2.x * vo2;
       if (EXTRA) w += c2.y * vo3;
       fv gop, gy, gyy;
-      bwd_moments<PPL>(vis, w, T_cur, ra, fac, tail, v, dy, qsum, gop, gy, gyy);
+      bwd_moments<PPL>(vis, w, T_cur, alpha, v, dy, R, gop, gy, gyy);
       // the colour sums of the lane's pixels (PPL = 2: one multiply + one scalar FMA per colour sum -- written on scalars:
       // from the 2-vector form the compiler builds v_mul + v_pk_fma and throws the packed op's upper half away)
       float g0s, g1s, g2s, g3 = 0.f;
@@ -724,6 +739,13 @@ __global__ __launch_bounds__(256) void splat_pack_kernel(size_t n, const float* 
                    colors ? colors[3 * e + 2] : 0.f, extra ? extra[e] : 0.f);
 }
 
+// GOL_RASTER_STAGE_MASK=0: the forward writes no wave masks and the backward runs its own reach test whatever it is handed
+// (A/B runs and the parity test; read on every call like GOL_RASTER_BG_GROUP -- they switch it inside one process)
+inline bool stage_mask_on() {
+  const char* e = getenv("GOL_RASTER_STAGE_MASK");
+  return !(e && e[0] == '0' && e[1] == 0);
+}
+
 }  // namespace
 
 // The forward's wave footprint for a launch of B views (GOL_RASTER_PPL = 1 | 2 overrides it for experiments).  One or two
@@ -776,7 +798,7 @@ extern "C" int gol_rasterize_fwd(int B, int N, int img_h, int img_w, int block, 
                                  float* out_extra, float* final_Ts, int32_t* final_idx, float* out_alpha,
                                  float* out_extra_norm, float norm_lo, const float* l1_target, const float* l1_mask,
                                  int l1_mask_c, uint8_t* l1_sign, float* l1_partial, float* l1_out, float l1_scale,
-                                 int pixels_per_lane, void* stream) {
+                                 uint8_t* stage_mask, int pixels_per_lane, void* stream) {
   GOL_RASTER_CHECK_DIMS(12, "image too large (32-bit byte offsets inside a view)");
   if (B == 0) return GOL_OK;
   GOL_REQUIRE(tile_bins && background && out_img && final_Ts && final_idx, "null pointer");
@@ -820,7 +842,7 @@ extern "C" int gol_rasterize_fwd(int B, int N, int img_h, int img_w, int block, 
       raster_fwd_kernel<EX, LZ, PPL><<<grid, 64 * Pix<PPL>::kWaves, 0, s>>>(
           N, img_h, img_w, planar, tiles_x, tiles_y, bins, sorted_ids, capacity, records, background, out_img, out_extra,
           final_Ts, final_idx, out_alpha, EX ? out_extra_norm : nullptr, norm_lo, l1_target, l1_mask, l1_mask_c, l1_sign,
-          l1_partial, B, bg_group, bg_vec16);
+          l1_partial, B, bg_group, bg_vec16, stage_mask_on() ? stage_mask : nullptr);
     });
   };
   const bool ex = out_extra || out_extra_norm;
@@ -841,7 +863,8 @@ extern "C" int gol_rasterize_bwd(int B, int N, int img_h, int img_w, int block, 
                                  const float* v_out_alpha, float* v_xy, float* v_conic, float* v_colors,
                                  float* v_extra, float* v_opacity, int grad_stride, const uint8_t* v_sign,
                                  const float* v_sign_mask, int v_sign_mask_c, const float* v_img_scale,
-                                 float v_img_scale_mul, int pixels_per_lane, void* stream) {
+                                 float v_img_scale_mul, const uint8_t* stage_mask, int stage_mask_ppl, int pixels_per_lane,
+                                 void* stream) {
   GOL_RASTER_CHECK_DIMS(0, "");   // 0: no 32-bit image offsets in this kernel, no image-size bound
   if (B == 0 || N == 0 || capacity == 0) return GOL_OK;
   GOL_REQUIRE(tile_bins && sorted_ids && background && final_Ts && final_idx, "null pointer");
@@ -862,7 +885,11 @@ extern "C" int gol_rasterize_bwd(int B, int N, int img_h, int img_w, int block, 
   const int2* bins = reinterpret_cast<const int2*>(tile_bins);
   hipStream_t s = (hipStream_t)stream;
   GOL_REQUIRE(pixels_per_lane >= 0 && pixels_per_lane <= 2, "pixels_per_lane: 0 (2), 1 or 2");
+  GOL_REQUIRE(stage_mask_ppl >= 0 && stage_mask_ppl <= 2, "stage_mask_ppl: the forward's pixels_per_lane (1 or 2), 0 = no masks");
   const int ppl = pixels_per_lane ? pixels_per_lane : 2;
+  // the forward's wave masks are this launch's only if it staged with the same footprints; else they are computed here
+  // (the forward writes them with two pixels per lane only, see raster_fwd_kernel)
+  const uint8_t* masks = (stage_mask && stage_mask_ppl == 2 && ppl == 2 && stage_mask_on()) ? stage_mask : nullptr;
   const bool ex = with_extra && (v_out_extra || v_extra);
   auto launch = [&](auto ex_c, auto packed_c) {
     with_ppl(ppl, [&](auto ppl_c) {
@@ -871,7 +898,7 @@ extern "C" int gol_rasterize_bwd(int B, int N, int img_h, int img_w, int block, 
       raster_bwd_kernel<EX, PK, PPL><<<grid, 64 * Pix<PPL>::kWaves, 0, s>>>(
           N, img_h, img_w, planar, tiles_x, tiles_y, bins, sorted_ids, capacity, records, background, final_Ts, final_idx,
           v_out_img, EX ? v_out_extra : nullptr, v_out_alpha, v_xy, v_conic, v_colors, EX ? v_extra : nullptr, v_opacity,
-          v_sign, v_sign_mask, v_sign_mask_c, v_img_scale, v_img_scale_mul, B);
+          v_sign, v_sign_mask, v_sign_mask_c, v_img_scale, v_img_scale_mul, B, masks);
     });
   };
   if (ex && packed) launch(kYes, kYes);

@@ -221,9 +221,8 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
   fv bgdot = 0.f;
 #pragma unroll
   for (int c = 0; c < CK; ++c) bgdot += ((c < nc) ? background[c0 + c] : 0.f) * vo[c];
-  const fv tail = T_final * (voa - bgdot);
   fv T_cur = T_final;
-  fv qsum = 0.f;  // running sum over the Gaussians behind of fac * <colour, v_out> (this chunk's channels)
+  fv R = bgdot - voa;  // composite of <colour, v_out> over what lies behind (this chunk's channels; see bwd_moments)
 
   float* acc_lane = &s_acc[wave][0][lane >> 4];  // this lane's column (lanes 15, 31, 47, 63 hold sums 4g + 0 .. 3)
   const int n_batches = (bmax - range.x + kBatchNdB) / kBatchNdB;
@@ -269,7 +268,7 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
 #pragma unroll
       for (int c = 0; c < CK; ++c) w += col[c] * vo[c];
       fv gop, gy, gyy;
-      bwd_moments<PPL>(vis, w, T_cur, ra, fac, tail, v, dy, qsum, gop, gy, gyy);
+      bwd_moments<PPL>(vis, w, T_cur, alpha, v, dy, R, gop, gy, gyy);
       float s[kRow];
 #pragma unroll
       for (int c = 0; c < CK; ++c) {

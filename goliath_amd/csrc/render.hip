@@ -39,6 +39,7 @@ static int render_layout(int B, int N, int img_h, int img_w, int64_t capacity, i
   L->tile_bins = take((int64_t)B * T * 2 * 4);
   L->keys = take((int64_t)B * cap * 8);
   L->sorted_ids = take((int64_t)B * cap * 4);
+  L->stage_mask = take((int64_t)B * cap);   // one byte per list entry, same index: the wave masks the raster forward staged
   L->n_isect = take((int64_t)B * 4);
   L->final_T = take((int64_t)B * P * 4);
   L->final_idx = take((int64_t)B * P * 4);
@@ -71,8 +72,8 @@ static int render_fwd_from(int B, int N, int img_h, int img_w, const float* xys,
                            capacity, records, with_depth ? 1 : 0, background, out_img,
                            with_depth ? out_depth : nullptr, at<float>(ws, L->final_T), at<int32_t>(ws, L->final_idx),
                            out_alpha, with_depth ? out_depth_norm : nullptr, norm_lo, l1_target, l1_mask, l1_mask_c,
-                           l1_target ? at<uint8_t>(ws, L->l1_sign) : nullptr, l1_partial, l1_out, l1_scale, 0,
-                           stream);
+                           l1_target ? at<uint8_t>(ws, L->l1_sign) : nullptr, l1_partial, l1_out, l1_scale,
+                           at<uint8_t>(ws, L->stage_mask), 0, stream);
 }
 
 // the raster backward into zeroed 64-byte gradient records
@@ -89,12 +90,15 @@ static int render_bwd_to_records(int B, int N, int img_h, int img_w, const float
   }
   float* g = grad_records;
   const bool use_depth = v_depth != nullptr;
+  int fwd_ppl = 0;   // the footprint render_fwd_from's raster launch of these B views staged its wave masks with
+  gol_raster_plan(B, &fwd_ppl);
   return gol_rasterize_bwd(B, N, img_h, img_w, 16, 1, at<int32_t>(ws, L->tile_bins), at<int32_t>(ws, L->sorted_ids),
                            capacity, records, use_depth ? 1 : 0, background,
                            at<float>(ws, L->final_T), at<int32_t>(ws, L->final_idx), v_img, v_depth, v_alpha, g + 4, g + 6,
                            g, use_depth ? g + 9 : nullptr, g + 3, GOL_GRAD_RECORD,
                            use_l1_sign ? at<uint8_t>(ws, L->l1_sign) : nullptr, use_l1_sign ? l1_mask : nullptr,
-                           use_l1_sign ? l1_mask_c : 0, v_img_scale, v_img_scale_mul, 0, stream);
+                           use_l1_sign ? l1_mask_c : 0, v_img_scale, v_img_scale_mul, at<uint8_t>(ws, L->stage_mask),
+                           fwd_ppl, 0, stream);
 }
 
 extern "C" int gol_render_fwd(int B, int N, int img_h, int img_w, float glob_scale, float clip_thresh, const float* means,

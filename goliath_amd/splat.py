@@ -231,23 +231,24 @@ def _abi_project_bwd(*, B, N, means3d, scales, glob_scale, quats, viewmats, intr
 def _abi_rasterize_fwd(*, B, N, img_h, img_w, planar, tile_bins, sorted_ids, capacity, records, with_extra, background,
                        out_img, out_extra=None, final_Ts, final_idx, out_alpha=None, out_extra_norm=None, norm_lo=0.0,
                        l1_target=None, l1_mask=None, l1_mask_c=0, l1_sign=None, l1_partial=None, l1_out=None,
-                       l1_scale=1.0, pixels_per_lane=0):
+                       l1_scale=1.0, stage_mask=None, pixels_per_lane=0):
     _lib.call("gol_rasterize_fwd", c_int(B), c_int(N), c_int(img_h), c_int(img_w), c_int(BLOCK), c_int(planar),
               _p(tile_bins, _I32), _p(sorted_ids, _I32), c_i64(capacity), _p(records), c_int(with_extra),
               _p(background), _p(out_img), _p(out_extra), _p(final_Ts), _p(final_idx, _I32), _p(out_alpha),
               _p(out_extra_norm), c_float(norm_lo), _p(l1_target), _p(l1_mask), c_int(l1_mask_c), _p(l1_sign, _U8),
-              _p(l1_partial), _p(l1_out), c_float(l1_scale), c_int(pixels_per_lane), stream_ptr())
+              _p(l1_partial), _p(l1_out), c_float(l1_scale), _p(stage_mask, _U8), c_int(pixels_per_lane), stream_ptr())
 
 
 def _abi_rasterize_bwd(*, B, N, img_h, img_w, planar, tile_bins, sorted_ids, capacity, records, with_extra, background,
                        final_Ts, final_idx, v_out_img=None, v_out_extra=None, v_out_alpha=None, v_xy, v_conic, v_colors,
                        v_extra=None, v_opacity, grad_stride=0, v_sign=None, v_sign_mask=None, v_sign_mask_c=0,
-                       v_img_scale=None, v_img_scale_mul=1.0, pixels_per_lane=0):
+                       v_img_scale=None, v_img_scale_mul=1.0, stage_mask=None, stage_mask_ppl=0, pixels_per_lane=0):
     _lib.call("gol_rasterize_bwd", c_int(B), c_int(N), c_int(img_h), c_int(img_w), c_int(BLOCK), c_int(planar),
               _p(tile_bins, _I32), _p(sorted_ids, _I32), c_i64(capacity), _p(records), c_int(with_extra), _p(background),
               _p(final_Ts), _p(final_idx, _I32), _p(v_out_img), _p(v_out_extra), _p(v_out_alpha), _p(v_xy), _p(v_conic),
               _p(v_colors), _p(v_extra), _p(v_opacity), c_int(grad_stride), _p(v_sign, _U8), _p(v_sign_mask),
-              c_int(v_sign_mask_c), _p(v_img_scale), c_float(v_img_scale_mul), c_int(pixels_per_lane), stream_ptr())
+              c_int(v_sign_mask_c), _p(v_img_scale), c_float(v_img_scale_mul), _p(stage_mask, _U8), c_int(stage_mask_ppl),
+              c_int(pixels_per_lane), stream_ptr())
 
 
 def _abi_rasterize_nd_fwd(*, B, N, C, img_h, img_w, tile_bins, sorted_ids, capacity, records, colors, background, out_img,
@@ -467,7 +468,7 @@ class RenderLayout(ctypes.Structure):
     """include/goliath_hip.h: gol_render_ws -- byte offsets of the sub-buffers of a render workspace."""
     _fields_ = [(n, ctypes.c_int64) for n in (
         "cov3d", "xys", "depths", "radii", "conics", "comp", "nth", "opac_eff", "records", "tile_count", "tile_bins",
-        "keys", "sorted_ids", "n_isect", "final_T", "final_idx", "l1_sign", "total")]
+        "keys", "sorted_ids", "n_isect", "final_T", "final_idx", "l1_sign", "stage_mask", "total")]
 
 
 _LAYOUTS = {}
@@ -492,6 +493,14 @@ def _ws_view(ws, off, dtype, shape):
     return ws[off:off + math.prod(shape) * dtype.itemsize].view(dtype).view(shape)
 
 
+def _fwd_ppl(B):
+    """gol_raster_plan: the wave footprint (pixels per lane) a raster forward of B views runs with when it is left the choice
+    -- what the staged forward below wrote its stage_mask with, as gol_render_bwd works it out for the fused call."""
+    ppl = c_int(0)
+    _lib.load().gol_raster_plan(c_int(B), ctypes.byref(ppl))   # (host only: not an ABI call the instrumented pass times)
+    return ppl.value
+
+
 def _render_fwd_staged(B, N, src, attrs, background, with_depth, norm_lo, cap, ws, L, out_img, out_depth, alpha, depth_norm,
                        l1_target, l1_mask, l1_mask_c, l1_partial, l1_out, l1_scale):
     """gol_render_fwd[_projected] stage by stage (what csrc/render.hip composes), for _lib.TIMING.  src: the views'
@@ -513,7 +522,7 @@ def _render_fwd_staged(B, N, src, attrs, background, with_depth, norm_lo, cap, w
                        final_idx=a + L.final_idx, out_alpha=alpha, out_extra_norm=depth_norm, norm_lo=norm_lo,
                        l1_target=l1_target, l1_mask=l1_mask, l1_mask_c=l1_mask_c,
                        l1_sign=a + L.l1_sign if l1_target is not None else None, l1_partial=l1_partial, l1_out=l1_out,
-                       l1_scale=l1_scale)
+                       l1_scale=l1_scale, stage_mask=a + L.stage_mask)
 
 
 def _render_bwd_staged(B, N, src, attrs, grads, background, cap, ws, L, v_img, v_depth, v_alpha, use_l1, l1_mask, v_scale,
@@ -531,7 +540,7 @@ def _render_bwd_staged(B, N, src, attrs, grads, background, cap, ws, L, v_img, v
                        v_extra=field(9) if use_depth else None, v_opacity=field(3), grad_stride=GRAD_RECORD,
                        v_sign=a + L.l1_sign if use_l1 else None, v_sign_mask=l1_mask,
                        v_sign_mask_c=0 if l1_mask is None else l1_mask.shape[1], v_img_scale=v_scale,
-                       v_img_scale_mul=v_scale_mul)
+                       v_img_scale_mul=v_scale_mul, stage_mask=a + L.stage_mask, stage_mask_ppl=_fwd_ppl(B))
     if attrs is not None:
         means, scales, quats, opacity = attrs
         v_mean, v_scale_g, v_quat, v_opacity = grads

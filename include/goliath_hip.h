@@ -170,6 +170,14 @@ int gol_bin_sort(int B, int N, const float* xys, const float* depths, const int3
  *   either way (a footprint only skips entries none of its pixels can take), up to the summation order of the gradient atomics.
  *   In the fused path (planar = 1) final_idx / l1_sign of pixels in tiles WITHOUT list entries are not written (the
  *   backward never reads them; final_T = 1 is).
+ * stage_mask[B,capacity] (NULL = off), one byte per list entry at the index of its sorted_ids entry: the forward stores the
+ *   wave mask it staged the entry with (bit w = the entry's alpha >= 1/255 region reaches the footprint of wave w; every
+ *   entry up to a tile's largest final_idx is written, a tile without entries writes nothing; a forward that runs with one
+ *   pixel per lane writes nothing at all).  The backward of the SAME
+ *   lists and records takes the buffer back with stage_mask_ppl = the pixels_per_lane that forward ran with (gol_raster_plan
+ *   for 0) and then skips its own reach test per entry -- the same bits, computed once; unless both ran with two pixels per lane, or if
+ *   stage_mask is NULL, it computes the masks itself.  GOL_RASTER_STAGE_MASK=0 in the
+ *   environment (set for the whole render, read per call) turns both sides off.
  * ---------------------------------------------------------------------------------------- */
 #define GOL_GRAD_RECORD 16
 #define GOL_SPLAT_RECORD 16
@@ -180,16 +188,16 @@ int gol_rasterize_fwd(int B, int N, int img_h, int img_w, int block, int planar,
                       const float* background, float* out_img,
                       float* out_extra, float* final_Ts, int32_t* final_idx, float* out_alpha,
                       float* out_extra_norm, float norm_lo, const float* l1_target, const float* l1_mask, int l1_mask_c,
-                      uint8_t* l1_sign, float* l1_partial, float* l1_out, float l1_scale, int pixels_per_lane,
-                      void* stream);
+                      uint8_t* l1_sign, float* l1_partial, float* l1_out, float l1_scale, uint8_t* stage_mask,
+                      int pixels_per_lane, void* stream);
 int gol_rasterize_bwd(int B, int N, int img_h, int img_w, int block, int planar, const int32_t* tile_bins,
                       const int32_t* sorted_ids, int64_t capacity, const float* records, int with_extra,
                       const float* background, const float* final_Ts,
                       const int32_t* final_idx, const float* v_out_img, const float* v_out_extra,
                       const float* v_out_alpha, float* v_xy, float* v_conic, float* v_colors,
                       float* v_extra, float* v_opacity, int grad_stride, const uint8_t* v_sign, const float* v_sign_mask,
-                      int v_sign_mask_c, const float* v_img_scale, float v_img_scale_mul, int pixels_per_lane,
-                      void* stream);
+                      int v_sign_mask_c, const float* v_img_scale, float v_img_scale_mul, const uint8_t* stage_mask,
+                      int stage_mask_ppl, int pixels_per_lane, void* stream);
 /* Diagnostic (bench.py's algorithmic roofline of the raster kernels): counts[B,2] (uint64) = per view the number of
  * (pixel, list entry) pairs up to the pixel's final_idx ("tested") and of those with alpha >= 1/255 ("taken" = composited),
  * from the state a planar gol_rasterize_fwd left (tile_bins, sorted_ids, records, final_idx). */
@@ -229,7 +237,8 @@ int gol_rasterize_nd_bwd(int B, int N, int C, int img_h, int img_w, int block, c
  * gol_render_bwd = gol_rasterize_bwd (64-byte gradient records, zeroed here) + gol_project_bwd, enqueued on `stream` out
  * of ONE caller-provided workspace.  gol_render_layout fills the byte offsets of the workspace's sub-buffers
  * (all 256-byte aligned; `total` = bytes to allocate) -- the caller reads n_isect[B] (int32, overflow check as for
- * gol_bin_sort), radii[B,N], final_T / final_idx[B,H,W], sorted_ids[B,capacity], tile_bins[B,T,2] there.
+ * gol_bin_sort), radii[B,N], final_T / final_idx[B,H,W], sorted_ids[B,capacity], tile_bins[B,T,2] there; stage_mask[B,capacity]
+ * (bytes) carries the raster forward's wave masks to gol_render_bwd.
  * The forward leaves everything the backward needs in the workspace: keep it (and the inputs) until gol_render_bwd.
  *   out_img[B,3,H,W]; out_alpha[B,H,W] = 1 - final_T; with_depth: out_depth_norm[B,H,W] = depth / clamp(alpha, norm_lo, 1)
  *   and optionally out_depth[B,H,W] (NULL = skip); l1_target / l1_mask / l1_partial[B,T] / l1_out (NULL = partial sums
@@ -241,7 +250,7 @@ int gol_rasterize_nd_bwd(int B, int N, int C, int img_h, int img_w, int block, c
  * ---------------------------------------------------------------------------------------- */
 typedef struct gol_render_ws {
   int64_t cov3d, xys, depths, radii, conics, comp, nth, opac_eff, records, tile_count, tile_bins, keys, sorted_ids,
-      n_isect, final_T, final_idx, l1_sign, total;
+      n_isect, final_T, final_idx, l1_sign, stage_mask, total;
 } gol_render_ws;
 int gol_render_layout(int B, int N, int img_h, int img_w, int64_t capacity, int with_l1, gol_render_ws* layout);
 int gol_render_fwd(int B, int N, int img_h, int img_w, float glob_scale, float clip_thresh, const float* means,
