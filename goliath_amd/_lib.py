@@ -35,6 +35,7 @@ _SYMBOLS = [
     "gol_mvp_template_fwd", "gol_mvp_template_bwd", "gol_mvp_primtransf_fwd", "gol_mvp_primtransf_bwd",
     "gol_envprefilter_scratch_floats", "gol_envprefilter_sg",
     "gol_trunk_conv_fwd", "gol_trunk_conv_bwd_scratch_floats", "gol_trunk_conv_bwd",
+    "gol_enc_conv_fwd", "gol_enc_conv_bwd_scratch_floats", "gol_enc_conv_bwd",
 ]
 
 

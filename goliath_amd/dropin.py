@@ -10,6 +10,7 @@
     dropin.patch_sh()             # optional: sh.dir2sh_torch and (with patch_rgca()) the frame's light SH on ONE HIP launch, no host sync
     dropin.patch_env_driver()     # optional: EnvSpinDecorator.forward's per-frame map rotation, light probe and mip scale on the GPU
     dropin.patch_env_prefilter()  # optional: envmap.prefilterEnvmapSG (the pyramid of _set_lightmap) on ONE HIP kernel per level
+    dropin.patch_encoder()        # optional: Encoder.forward's texture stack on the fused conv + bias + LeakyReLU operator
     dropin.set_environment(decorator, image)   # another environment map for a live EnvSpinDecorator, pyramid built on the GPU
 
 `install()` registers the module names the reference imports for its native code:
@@ -53,6 +54,20 @@ def patch_rgca(rgca_module=None):
     rgca_module.AutoEncoder.render = fused.autoencoder_render
     rgca_module.AutoEncoder.forward = fused.autoencoder_forward
     rgca_module.PrimDecoder.forward = fused.prim_decoder_forward
+    return rgca_module
+
+
+def patch_encoder(rgca_module=None):
+    """Opt in to the fused texture encoder: `Encoder.forward` (rgca.py:310-332) becomes goliath_amd.encoder.encoder_forward,
+    which runs the (Conv2dWNUB 4/2/1, LeakyReLU) pairs of `texmod` that goliath_amd.encoder.DISPATCH admits on
+    gol_enc_conv_fwd / _bwd and folds `color / 255.0 - 0.5` into the first layer's load when that layer is taken.  CPU
+    tensors and shapes that are not admitted take the module path: the reference's own lines, identical results.  Implies
+    none of the other patches; idempotent.  Returns the patched module."""
+    from . import encoder
+
+    if rgca_module is None:
+        import ca_code.models.rgca as rgca_module
+    rgca_module.Encoder.forward = encoder.encoder_forward
     return rgca_module
 
 

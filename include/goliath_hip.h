@@ -561,6 +561,33 @@ int gol_trunk_conv_bwd(int B, int Ci, int Co, int h, int w, float leak, const fl
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Encoder layer as one operator.  Replaces
+ *   Conv2dWNUB(Ci -> Co, 4, 2, 1) + LeakyReLU(leak)
+ * (ca_code/nn/layers.py:276-328,472, weight norm layers.py:157-244, stacked eight times at ca_code/models/rgca.py:281-298:
+ * one MIOpen convolution, an ATen add of the untied bias and an ATen leaky_relu per layer), and for the first layer the
+ * `color / 255.0 - 0.5` in front of the stack (rgca.py:314) as the affine (in_scale, in_shift) of the load:
+ *   xin[b,ci,r,c]  = in_scale * x[b,ci,r,c] + in_shift   inside the image, 0 outside (the zero pad comes AFTER the affine)
+ *   y[b,co,Y,X]    = lrelu( sum_{ci,ky,kx} xin[b,ci,2Y-1+ky,2X-1+kx] w_eff[co,ci,ky,kx] + bias[co,Y,X] )
+ *   x [B,Ci,H,W], H and W even; w_eff [Co,Ci,4,4] (the weight norm already applied, goliath_amd/tail.py:wn_weight);
+ *   bias [Co,H/2,W/2]; y [B,Co,H/2,W/2]; leak > 0.  fp32 MFMA, exact fp32.  Nothing but y is written.
+ * Co must be a multiple of 16 and Ci a multiple of 8 or one of 1..4 (a K stage is then zero-padded on the weight side; no
+ * channel of x that does not exist is read), H and W even: otherwise GOL_ERR_UNSUPPORTED.  w_eff, y, g_y and g_bias must
+ * be 16-byte aligned.
+ * bwd forms g_pre = g_y * (y > 0 ? 1 : leak) while loading (any of g_x / g_w / g_bias may be NULL = not wanted, at no cost):
+ *   g_x [B,Ci,H,W] written: in_scale * sum_{co,ky,kx} g_pre[b,co,Y,X] w_eff[co,ci,ky,kx] over 2Y-1+ky = r, 2X-1+kx = c;
+ *       needs w_eff in the forward's layout [Co,Ci,4,4] (no permuted copy);
+ *   g_w [Co,Ci,4,4] written (= sum_{b,Y,X} g_pre xin); needs x and scratch[gol_enc_conv_bwd_scratch_floats] (per-workgroup
+ *       partial sums added in a fixed order by a second kernel: no float atomics, bitwise reproducible);
+ *   g_bias [Co,H/2,W/2] written (= sum_b g_pre).
+ * ---------------------------------------------------------------------------------------- */
+int gol_enc_conv_fwd(int B, int Ci, int Co, int H, int W, float leak, float in_scale, float in_shift, const float* x,
+                     const float* w_eff, const float* bias, float* y, void* stream);
+long long gol_enc_conv_bwd_scratch_floats(int B, int Ci, int Co, int H, int W);
+int gol_enc_conv_bwd(int B, int Ci, int Co, int H, int W, float leak, float in_scale, float in_shift, const float* x,
+                     const float* w_eff, const float* y, const float* g_y, float* g_x, float* g_w, float* g_bias,
+                     float* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * SSIM image loss ("next" row).  Replaces `ssim` / `_ssim`
  * (ca_code/utils/ssim.py:25-65) as used by rgb_ssim (ca_code/loss/__init__.py:478-494): 11x11 Gaussian
  * window (sigma 1.5, zero padding), C1 = 0.01^2, C2 = 0.03^2, masked mean.
