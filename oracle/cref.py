@@ -95,11 +95,14 @@ def project_gaussians_backward(means3d, scales, glob_scale, quats, viewmat, fx, 
     v_mean = torch.zeros(N, 3)
     v_scale = torch.zeros(N, 3)
     v_quat = torch.zeros(N, 4)
+    # a converted copy must outlive the C call: _p() keeps an address only, so every conversion is bound to a local first
+    cov3d, conics, compensation, v_xy, v_depth, v_conic, v_compensation = map(
+        _f, (cov3d, conics, compensation, v_xy, v_depth, v_conic, v_compensation))
+    radii = radii.to(torch.int32).contiguous().cpu()
     lib().orc_project_bwd(c_int(N), _p(means3d), _p(scales), c_float(glob_scale), _p(quats),
-                          _p(viewmat), c_float(fx), c_float(fy), _p(_f(cov3d)),
-                          _p(radii.to(torch.int32).contiguous()), _p(_f(conics)),
-                          _p(_f(compensation)), _p(_f(v_xy)), _p(_f(v_depth)), _p(_f(v_conic)),
-                          _p(_f(v_compensation)), _p(v_cov2d), _p(v_cov3d), _p(v_mean),
+                          _p(viewmat), c_float(fx), c_float(fy), _p(cov3d), _p(radii), _p(conics),
+                          _p(compensation), _p(v_xy), _p(v_depth), _p(v_conic),
+                          _p(v_compensation), _p(v_cov2d), _p(v_cov3d), _p(v_mean),
                           _p(v_scale), _p(v_quat))
     return v_cov2d, v_cov3d, v_mean, v_scale, v_quat
 
@@ -128,8 +131,9 @@ def rasterize_forward(ids_sorted, tile_bins, xys, conics, colors, opacity, img_h
     out = torch.zeros(img_height, img_width, C)
     Ts = torch.zeros(img_height, img_width)
     idx = torch.zeros(img_height, img_width, dtype=torch.int32)
+    ids_sorted, tile_bins = ids_sorted.contiguous(), tile_bins.contiguous()
     lib().orc_rasterize_fwd(c_int(img_height), c_int(img_width), c_int(block_width), c_int(C),
-                            _p(ids_sorted.contiguous()), _p(tile_bins.contiguous()), _p(xys),
+                            _p(ids_sorted), _p(tile_bins), _p(xys),
                             _p(conics), _p(colors), _p(opacity), _p(background),
                             c_float(alpha_cap), _p(out), _p(Ts), _p(idx))
     return out, Ts, idx
@@ -145,11 +149,13 @@ def rasterize_backward(ids_sorted, tile_bins, xys, conics, colors, opacity, img_
     v_conic = torch.zeros(N, 3)
     v_col = torch.zeros(N, C)
     v_op = torch.zeros(N)
+    ids_sorted, tile_bins = ids_sorted.contiguous(), tile_bins.contiguous()
+    final_Ts, final_idx, v_out = _f(final_Ts), final_idx.to(torch.int32).contiguous(), _f(v_out)
+    v_out_alpha = None if v_out_alpha is None else _f(v_out_alpha)
     lib().orc_rasterize_bwd(c_int(img_height), c_int(img_width), c_int(block_width), c_int(C),
-                            c_int(N), _p(ids_sorted.contiguous()), _p(tile_bins.contiguous()),
+                            c_int(N), _p(ids_sorted), _p(tile_bins),
                             _p(xys), _p(conics), _p(colors), _p(opacity), _p(background),
-                            _p(_f(final_Ts)), _p(final_idx.to(torch.int32).contiguous()),
-                            _p(_f(v_out)), _p(None if v_out_alpha is None else _f(v_out_alpha)),
+                            _p(final_Ts), _p(final_idx), _p(v_out), _p(v_out_alpha),
                             c_float(alpha_cap_bwd), _p(v_xy), _p(v_conic), _p(v_col), _p(v_op))
     return v_xy, v_conic, v_col, v_op[:, None]
 
@@ -183,9 +189,9 @@ def evaluate_gaussian_fwd(lobe_dirs, lobe_sigmas, light_values, light_pts, prim_
     N, D = lobe_dirs.shape[:2]
     L = light_values.shape[1]
     out = torch.empty(N, D, 3)
+    n_lights = n_lights.to(torch.int32).contiguous().cpu()
     lib().orc_sg_fwd(c_int(N), c_int(D), c_int(L), _p(lobe_dirs), _p(lobe_sigmas), _p(light_values),
-                     _p(light_pts), _p(prim_pts), _p(n_lights.to(torch.int32).contiguous().cpu()),
-                     c_int(w_type), _p(out))
+                     _p(light_pts), _p(prim_pts), _p(n_lights), c_int(w_type), _p(out))
     return out
 
 
@@ -199,9 +205,9 @@ def evaluate_gaussian_bwd(lobe_dirs, lobe_sigmas, light_values, light_pts, prim_
     gd = torch.zeros(N, D, 3)
     gs = torch.zeros(lobe_sigmas.shape)
     gl = torch.zeros(N, L, 3) if want_light_grad else None
+    n_lights = n_lights.to(torch.int32).contiguous().cpu()
     lib().orc_sg_bwd(c_int(N), c_int(D), c_int(L), _p(lobe_dirs), _p(lobe_sigmas), _p(light_values),
-                     _p(light_pts), _p(prim_pts), _p(n_lights.to(torch.int32).contiguous().cpu()),
-                     _p(grad_integral), c_int(w_type), _p(gd), _p(gs), _p(gl))
+                     _p(light_pts), _p(prim_pts), _p(n_lights), _p(grad_integral), c_int(w_type), _p(gd), _p(gs), _p(gl))
     return gd, gs, gl
 
 

@@ -1,8 +1,9 @@
 """oracle/cref64.py -- TEST INFRASTRUCTURE ONLY.
 
 fp64 twins (orc64_*) of the gsplat restatement's projection / rasterization passes (oracle/gsplat_oracle.c compiled
-with -DORC_FP64).  Used by tests/test_oracle_gsplat_fd.py only: finite differences of the fp64 FORWARD against the
-hand-written BACKWARD, with the tile lists frozen (the lists are piecewise constant in the inputs)."""
+with -DORC_FP64).  Used by tests/test_oracle_gsplat_fd.py (finite differences of the fp64 FORWARD against the hand-written
+BACKWARD, with the tile lists frozen: the lists are piecewise constant in the inputs) and by tests/project_cases.py (the
+float64 judge of the projection at the frustum's edges)."""
 import ctypes
 
 import torch
@@ -38,10 +39,13 @@ def project_bwd(means, scales, glob_scale, quats, viewmat, fx, fy, cov3d, radii,
     N = means.shape[0]
     z = lambda *s: torch.zeros(*s, dtype=torch.float64)
     v_cov2d, v_cov3d, v_mean, v_scale, v_quat = z(N, 3), z(N, 6), z(N, 3), z(N, 3), z(N, 4)
+    # a converted copy must outlive the C call: _p() keeps an address only, so every conversion is bound to a local first
+    cov3d, conics, comp, v_xy, v_depth, v_conic, v_comp = map(_d, (cov3d, conics, comp, v_xy, v_depth, v_conic, v_comp))
+    radii = radii.to(torch.int32).contiguous().cpu()
     cref.lib().orc64_project_bwd(c_int(N), _p(means), _p(scales), c_double(glob_scale), _p(quats), _p(viewmat),
-                                 c_double(fx), c_double(fy), _p(_d(cov3d)), _p(radii.to(torch.int32).contiguous()),
-                                 _p(_d(conics)), _p(_d(comp)), _p(_d(v_xy)), _p(_d(v_depth)), _p(_d(v_conic)),
-                                 _p(_d(v_comp)), _p(v_cov2d), _p(v_cov3d), _p(v_mean), _p(v_scale), _p(v_quat))
+                                 c_double(fx), c_double(fy), _p(cov3d), _p(radii), _p(conics), _p(comp), _p(v_xy),
+                                 _p(v_depth), _p(v_conic), _p(v_comp), _p(v_cov2d), _p(v_cov3d), _p(v_mean), _p(v_scale),
+                                 _p(v_quat))
     return v_mean, v_scale, v_quat
 
 
@@ -51,7 +55,8 @@ def rasterize_fwd(ids, bins, xys, conics, colors, opacity, H, W, block, backgrou
     out = torch.zeros(H, W, C, dtype=torch.float64)
     Ts = torch.zeros(H, W, dtype=torch.float64)
     idx = torch.zeros(H, W, dtype=torch.int32)
-    cref.lib().orc64_rasterize_fwd(c_int(H), c_int(W), c_int(block), c_int(C), _p(ids.contiguous()), _p(bins.contiguous()),
+    ids, bins = ids.contiguous(), bins.contiguous()
+    cref.lib().orc64_rasterize_fwd(c_int(H), c_int(W), c_int(block), c_int(C), _p(ids), _p(bins),
                                    _p(xys), _p(conics), _p(colors), _p(opacity), _p(background), c_double(alpha_cap),
                                    _p(out), _p(Ts), _p(idx))
     return out, Ts, idx
@@ -63,9 +68,11 @@ def rasterize_bwd(ids, bins, xys, conics, colors, opacity, H, W, block, backgrou
     N, C = colors.shape
     z = lambda *s: torch.zeros(*s, dtype=torch.float64)
     v_xy, v_conic, v_col, v_op = z(N, 2), z(N, 3), z(N, C), z(N)
-    cref.lib().orc64_rasterize_bwd(c_int(H), c_int(W), c_int(block), c_int(C), c_int(N), _p(ids.contiguous()),
-                                   _p(bins.contiguous()), _p(xys), _p(conics), _p(colors), _p(opacity), _p(background),
-                                   _p(_d(Ts)), _p(idx.contiguous()), _p(_d(v_out)),
-                                   _p(None if v_out_alpha is None else _d(v_out_alpha)), c_double(alpha_cap_bwd),
+    ids, bins, idx = ids.contiguous(), bins.contiguous(), idx.contiguous()
+    Ts, v_out = _d(Ts), _d(v_out)
+    v_out_alpha = None if v_out_alpha is None else _d(v_out_alpha)
+    cref.lib().orc64_rasterize_bwd(c_int(H), c_int(W), c_int(block), c_int(C), c_int(N), _p(ids),
+                                   _p(bins), _p(xys), _p(conics), _p(colors), _p(opacity), _p(background),
+                                   _p(Ts), _p(idx), _p(v_out), _p(v_out_alpha), c_double(alpha_cap_bwd),
                                    _p(v_xy), _p(v_conic), _p(v_col), _p(v_op))
     return v_xy, v_conic, v_col, v_op
