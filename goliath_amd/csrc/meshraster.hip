@@ -154,12 +154,14 @@ constexpr int kRasterWgs = 4096;  // persistent workgroups of the raster kernel
 // prefix[b] <= e < prefix[b + 1], tile e - prefix[b] of the view's box, row-major): a fixed grid strides over the list.
 // Launching one workgroup per tile of every image made the kernel dispatch-bound: 131 k workgroups of which ~3 k had
 // work took 0.15 ms at the ~1 workgroup/ns the dispatcher sustains (profiles/r03g_urhand_kernel_trace.txt).
-__global__ __launch_bounds__(256) void mesh_raster_kernel(int B, int F, int H, int W, const FaceRec* __restrict__ rec,
-                                                          const uint2* __restrict__ bounds,
-                                                          const int32_t* __restrict__ box,
-                                                          const int32_t* __restrict__ prefix,
-                                                          int32_t* __restrict__ index_img, float* __restrict__ depth_img,
-                                                          float* __restrict__ bary_img) {
+// kFlat: every face at one depth (the UV triangles of csrc/uvtopo.hip, all at z = 1) -- no depth test at all, the lowest
+// covering face index wins and the depth written is 1.  (With the depth test the winner among coplanar faces would be
+// decided by the last bit of w0 + w1 + w2, which is 1 only up to rounding.)
+template <bool kFlat>
+__device__ __forceinline__ void mesh_raster_body(int B, int F, int H, int W, const FaceRec* __restrict__ rec,
+                                                 const uint2* __restrict__ bounds, const int32_t* __restrict__ box,
+                                                 const int32_t* __restrict__ prefix, int32_t* __restrict__ index_img,
+                                                 float* __restrict__ depth_img, float* __restrict__ bary_img) {
   __shared__ int32_t s_face[kFaceRound];
   __shared__ float4 s_rec[3][256];
   __shared__ int32_t s_count;
@@ -218,7 +220,10 @@ __global__ __launch_bounds__(256) void mesh_raster_kernel(int B, int F, int H, i
           const float E1 = q0.z * dx + q0.w * dy;
           const float E2 = q1.x * dx + q1.y * dy;
           const float E0 = q2.z - E1 - E2;
-          if (E0 >= 0.f && E1 >= 0.f && E2 >= 0.f) {
+          if (kFlat) {
+            const int fi = __float_as_int(q2.y);
+            if (E0 >= 0.f && E1 >= 0.f && E2 >= 0.f && (best < 0 || fi < best)) { best = fi; best_iz = 1.f; }
+          } else if (E0 >= 0.f && E1 >= 0.f && E2 >= 0.f) {
             const float w0 = (E0 * q2.w) * q1.z, w1 = (E1 * q2.w) * q1.w, w2 = (E2 * q2.w) * q2.x;
             const float iz = w0 + w1 + w2;  // 1 / depth at the sample
             const int fi = __float_as_int(q2.y);
@@ -244,6 +249,24 @@ __global__ __launch_bounds__(256) void mesh_raster_kernel(int B, int F, int H, i
   }
 }
 
+__global__ __launch_bounds__(256) void mesh_raster_kernel(int B, int F, int H, int W, const FaceRec* __restrict__ rec,
+                                                          const uint2* __restrict__ bounds,
+                                                          const int32_t* __restrict__ box,
+                                                          const int32_t* __restrict__ prefix,
+                                                          int32_t* __restrict__ index_img, float* __restrict__ depth_img,
+                                                          float* __restrict__ bary_img) {
+  mesh_raster_body<false>(B, F, H, W, rec, bounds, box, prefix, index_img, depth_img, bary_img);
+}
+
+__global__ __launch_bounds__(256) void mesh_raster_flat_kernel(int B, int F, int H, int W, const FaceRec* __restrict__ rec,
+                                                               const uint2* __restrict__ bounds,
+                                                               const int32_t* __restrict__ box,
+                                                               const int32_t* __restrict__ prefix,
+                                                               int32_t* __restrict__ index_img,
+                                                               float* __restrict__ depth_img) {
+  mesh_raster_body<true>(B, F, H, W, rec, bounds, box, prefix, index_img, depth_img, nullptr);
+}
+
 }  // namespace
 
 extern "C" int64_t gol_mesh_raster_workspace_bytes(int B, int F) {
@@ -252,14 +275,35 @@ extern "C" int64_t gol_mesh_raster_workspace_bytes(int B, int F) {
          (int64_t)B * F * (int64_t)sizeof(uint2) + ((int64_t)B + 1) * (int64_t)sizeof(int32_t);
 }
 
+static int mesh_raster_run(bool flat, int B, int V, int F, int H, int W, const float* v_pix, const int32_t* vi,
+                           int32_t* index_img, float* depth_img, float* bary_img, void* workspace, void* stream);
+
 extern "C" int gol_mesh_raster(int B, int V, int F, int H, int W, const float* v_pix, const int32_t* vi,
                                int32_t* index_img, float* depth_img, float* bary_img, void* workspace, void* stream) {
-  GOL_REQUIRE(B >= 0 && V >= 0 && F >= 0 && H > 0 && W > 0, "bad size");
-  GOL_REQUIRE(B <= 65535 && H <= 16 * 65535 && W <= 16 * 65535, "size out of range");  // (tile bounds are packed in 16 bits)
+  return mesh_raster_run(false, B, V, F, H, W, v_pix, vi, index_img, depth_img, bary_img, workspace, stream);
+}
+
+extern "C" int gol_mesh_raster_flat(int B, int V, int F, int H, int W, const float* v_pix, const int32_t* vi,
+                                    int32_t* index_img, float* depth_img, void* workspace, void* stream) {
+  return mesh_raster_run(true, B, V, F, H, W, v_pix, vi, index_img, depth_img, nullptr, workspace, stream);
+}
+
+#define RASTER_REQUIRE(cond, msg)            \
+  do {                                       \
+    if (!(cond)) {                           \
+      gol_set_error("%s: %s", who, msg);     \
+      return GOL_ERR_INVALID_ARG;            \
+    }                                        \
+  } while (0)
+static int mesh_raster_run(bool flat, int B, int V, int F, int H, int W, const float* v_pix, const int32_t* vi,
+                           int32_t* index_img, float* depth_img, float* bary_img, void* workspace, void* stream) {
+  const char* who = flat ? "gol_mesh_raster_flat" : "gol_mesh_raster";   // (errors name the entry that was called)
+  RASTER_REQUIRE(B >= 0 && V >= 0 && F >= 0 && H > 0 && W > 0, "bad size");
+  RASTER_REQUIRE(B <= 65535 && H <= 16 * 65535 && W <= 16 * 65535, "size out of range");  // (tile bounds are packed in 16 bits)
   if (B == 0) return GOL_OK;
-  GOL_REQUIRE(index_img && depth_img, "null output");
-  GOL_REQUIRE(workspace != nullptr, "null workspace");
-  GOL_REQUIRE(F == 0 || (v_pix && vi), "null input");
+  RASTER_REQUIRE(index_img && depth_img, "null output");
+  RASTER_REQUIRE(workspace != nullptr, "null workspace");
+  RASTER_REQUIRE(F == 0 || (v_pix && vi), "null input");
   hipStream_t s = (hipStream_t)stream;
   FaceRec* rec = reinterpret_cast<FaceRec*>(workspace);
   int32_t* box = reinterpret_cast<int32_t*>(rec + (size_t)B * F);  // [B,4] behind the face records
@@ -280,8 +324,15 @@ extern "C" int gol_mesh_raster(int B, int V, int F, int H, int W, const float* v
     mesh_clear_kernel<int32_t, float><<<2048, 256, 0, s>>>(npix, index_img, depth_img, 3 * npix, bary_img, -1, 0.f);
   if (F > 0) {
     tile_prefix_kernel<<<1, 1024, 0, s>>>(B, box, prefix);
-    mesh_raster_kernel<<<kRasterWgs, 256, 0, s>>>(B, F, H, W, rec, bounds, box, prefix, index_img, depth_img, bary_img);
+    if (flat)
+      mesh_raster_flat_kernel<<<kRasterWgs, 256, 0, s>>>(B, F, H, W, rec, bounds, box, prefix, index_img, depth_img);
+    else
+      mesh_raster_kernel<<<kRasterWgs, 256, 0, s>>>(B, F, H, W, rec, bounds, box, prefix, index_img, depth_img, bary_img);
   }
-  GOL_CHECK_LAUNCH();
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) {
+    gol_set_error("%s: %s", who, hipGetErrorString(e));
+    return GOL_ERR_LAUNCH;
+  }
   return GOL_OK;
 }
+#undef RASTER_REQUIRE

@@ -5,6 +5,8 @@
     dropin.patch_rgca()           # optional: fused shading tail + batched, sync-free render
     dropin.patch_light_decorator()  # optional: the env-relight driver hands over ONE shared pyramid (config 2)
     dropin.patch_geometry()       # optional: GeometryModule.to_uv / .vn and the decoder's postex / tn on the uvgeom kernels
+    dropin.install_pytorch3d_shim()  # optional, before importing ca_code.*: lets geom / urhand / hand_mvp import without pytorch3d
+    dropin.patch_geometry_ctor()  # optional: GeometryModule(...) builds its index / bary / face images (and the impaint) on HIP
     dropin.patch_lbs()            # optional: LinearBlendSkinning / LBSModule.pose on the fused skeleton + skinning kernels
     dropin.patch_relight_vis()    # optional, with patch_rgca(): run_vis_relight's frames from ONE render + the HIP env background
     dropin.patch_sh()             # optional: sh.dir2sh_torch and (with patch_rgca()) the frame's light SH on ONE HIP launch, no host sync
@@ -21,6 +23,7 @@
 so `run_train.py` / `run_vis_relight.py` need no edit.  `patch_rgca()` additionally swaps the two
 Python-level hot spots of ca_code.models.rgca for their fused equivalents (same signatures/returns).
 """
+import importlib.machinery
 import sys
 import types
 
@@ -136,6 +139,145 @@ def patch_geometry(geom_module=None):
     geom_module.GeometryModule.to_uv = uvgeom.geometry_to_uv
     geom_module.GeometryModule.vn = uvgeom.geometry_vn
     return geom_module
+
+
+def patch_geometry_ctor(geom_module=None):
+    """Rebind `geom.make_uv_face_index` (ca_code/utils/geom.py:31-66: pytorch3d's CUDA rasterize_meshes) and
+    `geom.index_image_impaint` (geom.py:145-194: a scikit-learn KD-tree on the host) to goliath_amd.uvtopo
+    (gol_mesh_raster on the UV triangles, gol_nearest_valid), so that an unmodified `GeometryModule(...)` and
+    `render_index_images(...)` build their index / barycentric / face images without either package; the reference's own
+    make_uv_vert_index, make_uv_barys and bary_coords keep running on the face image they are handed.  Like the reference
+    the replacements accept the constructor's CPU buffers: the work runs on `device` (default "cuda") and the impainted
+    images come back where the inputs were.  Conventions (what is pinned by the reference, what is stated): see
+    goliath_amd/uvtopo.py.  Idempotent.  Returns the patched module."""
+    from . import uvtopo
+
+    if geom_module is None:
+        import ca_code.utils.geom as geom_module
+
+    def make_uv_face_index(vt, vti, uv_shape, flip_uv=True, device=None):
+        return uvtopo.uv_face_index(vt, vti, uv_shape, flip_uv=flip_uv, device="cuda" if device is None else device)
+
+    def index_image_impaint(index_image, bary_image=None, distance_threshold=100.0):
+        device = None if index_image.is_cuda and (bary_image is None or bary_image.is_cuda) else "cuda"
+        return uvtopo.impaint(index_image, bary_image, distance_threshold, device=device)
+
+    geom_module.make_uv_face_index = make_uv_face_index
+    geom_module.index_image_impaint = index_image_impaint
+    return geom_module
+
+
+def _pytorch3d_placeholder(name):
+    def placeholder(*args, **kwargs):
+        raise RuntimeError(f"pytorch3d.{name} is a placeholder: pytorch3d is not installed.  The UV index images of "
+                           "GeometryModule are built without it after goliath_amd.dropin.patch_geometry_ctor(); the "
+                           "pytorch3d mesh renderer has no stand-in (use goliath_amd.meshraster.RenderLayer)")
+
+    placeholder.__name__ = placeholder.__qualname__ = name.rsplit(".", 1)[-1]
+    return placeholder
+
+
+def axis_angle_to_matrix(axis_angle):
+    """pytorch3d.transforms.axis_angle_to_matrix restated in plain torch: [..., 3] -> [..., 3, 3], Rodrigues' formula
+    R = I + (sin t / t) K + ((1 - cos t) / t^2) K^2 with K the cross-product matrix of the vector, t its length (the two
+    ratios by their Taylor series below t = 1e-4)."""
+    import torch
+
+    t2 = (axis_angle * axis_angle).sum(-1)
+    t = t2.sqrt()
+    small = t < 1e-4
+    ts = torch.where(small, torch.ones_like(t), t)
+    a = torch.where(small, 1.0 - t2 / 6.0, ts.sin() / ts)
+    b = torch.where(small, 0.5 - t2 / 24.0, (1.0 - ts.cos()) / (ts * ts))
+    x, y, z = axis_angle.unbind(-1)
+    o = torch.zeros_like(x)
+    K = torch.stack([o, -z, y, z, o, -x, -y, x, o], -1).reshape(axis_angle.shape[:-1] + (3, 3))
+    eye = torch.eye(3, dtype=axis_angle.dtype, device=axis_angle.device)
+    return eye + a[..., None, None] * K + b[..., None, None] * (K @ K)
+
+
+def euler_angles_to_matrix(euler_angles, convention):
+    """pytorch3d.transforms.euler_angles_to_matrix restated: [..., 3] angles in radians and a convention of three letters
+    out of "XYZ" -> the product R_c0(a0) R_c1(a1) R_c2(a2) of the elementary right-handed rotations, [..., 3, 3]."""
+    import torch
+
+    if len(convention) != 3 or any(c not in "XYZ" for c in convention) or convention[1] in (convention[0], convention[2]):
+        raise ValueError(f"invalid convention {convention!r}")
+
+    def axis(letter, angle):
+        c, s, o, l = angle.cos(), angle.sin(), torch.zeros_like(angle), torch.ones_like(angle)
+        flat = {"X": (l, o, o, o, c, -s, o, s, c), "Y": (c, o, s, o, l, o, -s, o, c), "Z": (c, -s, o, s, c, o, o, o, l)}[letter]
+        return torch.stack(flat, -1).reshape(angle.shape + (3, 3))
+
+    m = [axis(c, a) for c, a in zip(convention, euler_angles.unbind(-1))]
+    return m[0] @ m[1] @ m[2]
+
+
+def matrix_to_axis_angle(matrix):
+    """pytorch3d.transforms.matrix_to_axis_angle restated: rotation matrices [..., 3, 3] -> axis * angle [..., 3], angle in
+    [0, pi].  Through the unit quaternion with the larger of the four candidate components as pivot (stable at every
+    angle, pi included), w made non-negative, angle = 2 atan2(|xyz|, w)."""
+    import torch
+
+    m = matrix
+    m00, m11, m22 = m[..., 0, 0], m[..., 1, 1], m[..., 2, 2]
+    q_abs = torch.stack([1.0 + m00 + m11 + m22, 1.0 + m00 - m11 - m22, 1.0 - m00 + m11 - m22, 1.0 - m00 - m11 + m22], -1)
+    q_abs = q_abs.clamp(min=0.0).sqrt()                       # 2 |w|, 2 |x|, 2 |y|, 2 |z|
+    cand = torch.stack([
+        torch.stack([q_abs[..., 0] ** 2, m[..., 2, 1] - m[..., 1, 2], m[..., 0, 2] - m[..., 2, 0], m[..., 1, 0] - m[..., 0, 1]], -1),
+        torch.stack([m[..., 2, 1] - m[..., 1, 2], q_abs[..., 1] ** 2, m[..., 1, 0] + m[..., 0, 1], m[..., 0, 2] + m[..., 2, 0]], -1),
+        torch.stack([m[..., 0, 2] - m[..., 2, 0], m[..., 1, 0] + m[..., 0, 1], q_abs[..., 2] ** 2, m[..., 1, 2] + m[..., 2, 1]], -1),
+        torch.stack([m[..., 1, 0] - m[..., 0, 1], m[..., 2, 0] + m[..., 0, 2], m[..., 2, 1] + m[..., 1, 2], q_abs[..., 3] ** 2], -1),
+    ], -2)                                                    # [..., 4 pivots, 4]: 4 p (w, x, y, z) for pivot p
+    pivot = q_abs.argmax(-1)
+    q = torch.gather(cand, -2, pivot[..., None, None].expand(pivot.shape + (1, 4)))[..., 0, :]
+    q = q / (2.0 * torch.gather(q_abs, -1, pivot[..., None]).clamp(min=0.1))
+    q = torch.where(q[..., :1] < 0, -q, q)
+    n = q[..., 1:].norm(dim=-1, keepdim=True)
+    angle = 2.0 * torch.atan2(n, q[..., :1])
+    # angle / |xyz|: 2 / w-ish near 0 (sin(t/2) ~ t/2 -> factor 2)
+    factor = torch.where(n < 1e-6, torch.full_like(n, 2.0), angle / n.clamp(min=1e-30))
+    return q[..., 1:] * factor
+
+
+def install_pytorch3d_shim():
+    """Where `import pytorch3d` fails, register the least of it that lets `ca_code.utils.geom`, `ca_code.models.urhand`
+    and `ca_code.models.hand_mvp` import: `pytorch3d.transforms.axis_angle_to_matrix`, `euler_angles_to_matrix` and
+    `matrix_to_axis_angle` (urhand.py:773 calls them every frame) as the plain-torch restatements above; `Meshes`,
+    `rasterize_meshes`, `TexturesUV`, `MeshRasterizer`, `RasterizationSettings`, `cameras_from_opencv_projection`,
+    `load_ply` and `save_ply` as placeholders whose call raises an error naming patch_geometry_ctor().  Does nothing when
+    the real package imports.  Returns the list of module names it registered."""
+    try:
+        import pytorch3d  # noqa: F401
+
+        return []
+    except ImportError:
+        pass
+    layout = {
+        "pytorch3d": {},
+        "pytorch3d.structures": {"Meshes": None},
+        "pytorch3d.renderer": {"MeshRasterizer": None, "RasterizationSettings": None},
+        "pytorch3d.renderer.mesh": {},
+        "pytorch3d.renderer.mesh.rasterize_meshes": {"rasterize_meshes": None},
+        "pytorch3d.renderer.mesh.textures": {"TexturesUV": None},
+        "pytorch3d.utils": {"cameras_from_opencv_projection": None},
+        "pytorch3d.io": {"load_ply": None, "save_ply": None},
+        "pytorch3d.transforms": {"axis_angle_to_matrix": axis_angle_to_matrix,
+                                 "euler_angles_to_matrix": euler_angles_to_matrix,
+                                 "matrix_to_axis_angle": matrix_to_axis_angle},
+    }
+    for name, attrs in layout.items():
+        m = types.ModuleType(name)
+        m.__path__ = []           # a package: `import pytorch3d.renderer.mesh.textures` walks the chain
+        m.__spec__ = importlib.machinery.ModuleSpec(name, None, is_package=True)   # importlib.util.find_spec() needs one
+        for attr, obj in attrs.items():
+            setattr(m, attr, obj if obj is not None else _pytorch3d_placeholder(f"{name[len('pytorch3d.'):]}.{attr}"))
+        sys.modules[name] = m
+    for name in layout:          # parents carry their children as attributes
+        parent, _, child = name.rpartition(".")
+        if parent:
+            setattr(sys.modules[parent], child, sys.modules[name])
+    return list(layout)
 
 
 def patch_lbs(lbs_module=None):

@@ -660,6 +660,12 @@ int gol_imgtail_bwd(int B, int H, int W, const float* rgb, const float* alpha, c
 int64_t gol_mesh_raster_workspace_bytes(int B, int F);
 int gol_mesh_raster(int B, int V, int F, int H, int W, const float* v_pix, const int32_t* vi, int32_t* index_img,
                     float* depth_img, float* bary_img, void* workspace, void* stream);
+/* gol_mesh_raster_flat: the same rasteriser (same setup, coverage rules, workspace and images) for a mesh whose faces all
+ * lie at ONE depth, such as UV triangles: z only has to be > 0, there is no depth test, among the faces that cover a
+ * sample the LOWEST FACE INDEX wins, and depth_img holds 1 where covered.  (gol_mesh_raster's tie rule needs exactly
+ * equal interpolated depths; for coplanar faces those differ in the last bit of w0 + w1 + w2.)  No barycentric image. */
+int gol_mesh_raster_flat(int B, int V, int F, int H, int W, const float* v_pix, const int32_t* vi, int32_t* index_img,
+                         float* depth_img, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Textured mesh render after gol_mesh_raster, forward and backward: the rest of the reference's drtk layer
@@ -735,6 +741,40 @@ int gol_uvgeom_bwd(int B, int V, int F, int S, int T, int I, const float* verts,
                    const int32_t* item_start, const int32_t* item_tid, const int32_t* texel_of, const int32_t* vt_start,
                    const int32_t* vt_slot, float vn_eps, float norm_eps, const float* vn, const float* g_postex,
                    const float* g_tn, float* item_sums, float* g_s, float* g_verts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * uvtopo: the constant UV topology images GeometryModule.__init__ registers (ca_code/utils/geom.py:197-249), without
+ * pytorch3d and without the KD-tree (csrc/uvtopo.hip).  Built once per model; forward only, no atomics, reproducible.
+ * Texel (r, c) of an [H,W] image is sampled at uv = ((c + 0.5) / W, (r + 0.5) / H); flip_uv != 0 mirrors v (1 - v, in
+ * fp32) first.  That sample point is the reference's own (geom.py:133-139) and so are the barycentric arithmetic and the
+ * impaint semantics; coverage exactly ON an edge (covered here) and the winner among overlapping faces (lowest index)
+ * are this library's stated conventions: pytorch3d's are not in the reference tree.
+ * gol_uv_face_index: make_uv_face_index (geom.py:31-66) after its `1 - vt`: face_img[H,W] int32 = the UV triangle
+ *   vti[F,3] (int32 ids into vt[Vt,2]) that holds the texel's sample, -1 = none, by gol_mesh_raster_flat on
+ *   v_pix = (u W, v H, 1): gol_mesh_raster's coverage rules, the lowest face index where faces overlap.  workspace: gol_uv_face_index_workspace_bytes(Vt, F, H, W)
+ *   bytes, 16-byte aligned.
+ * gol_uv_topology: make_uv_vert_index (geom.py:69-83), make_uv_barys / bary_coords (geom.py:86-142) and the valid mask
+ *   (geom.py:228) from face_img: index_image[H,W,3] int64 = vi[face] (-1 where empty), face_index_image[H,W] int64,
+ *   bary_image[H,W,3] = bary_coords of the sample in the triangle's uv (anchored at its third vertex, denom clamped away
+ *   from 0 by 1e-6 keeping its sign, b2 = 1 - b0 - b1; no contraction; 0 where empty), valid_mask[H,W] bytes 0 / 1.
+ *   A face id outside [0, F) or a uv id outside [0, Vt) counts as empty.  Every element is written.
+ * gol_nearest_valid: the KD-tree query of index_image_impaint (geom.py:158-172): for every texel with valid == 0 the
+ *   valid texel at the smallest squared distance over integer (row, col), ties to the lexicographically smallest
+ *   (row, col), accepted while d^2 <= max_d2: src[H,W] int32 = row * W + col of the source, -1 for valid texels and for
+ *   texels without an accepted source (every element written).  col_near[H,W] int32 is scratch.  H <= 65535.
+ * gol_impaint_gather: the copies of geom.py:180-191 / 238-244 for up to three images at once, as 4-byte words:
+ *   out_k[p] = in_k[src[p] >= 0 ? src[p] : p] for the w_k words of texel p (int64 x 3: w = 6; fp32 x 3: w = 3; in_k NULL =
+ *   image absent); out of place.
+ * ---------------------------------------------------------------------------------------- */
+int64_t gol_uv_face_index_workspace_bytes(int Vt, int F, int H, int W);
+int gol_uv_face_index(int Vt, int F, int H, int W, int flip_uv, const float* vt, const int32_t* vti, int32_t* face_img,
+                      void* workspace, void* stream);
+int gol_uv_topology(int F, int Vt, int H, int W, int flip_uv, const int32_t* face_img, const int32_t* vi,
+                    const int32_t* vti, const float* vt, int64_t* index_image, int64_t* face_index_image,
+                    float* bary_image, uint8_t* valid_mask, void* stream);
+int gol_nearest_valid(int H, int W, int64_t max_d2, const uint8_t* valid, int32_t* col_near, int32_t* src, void* stream);
+int gol_impaint_gather(int64_t P, const int32_t* src, int w0, const uint32_t* in0, uint32_t* out0, int w1,
+                       const uint32_t* in1, uint32_t* out1, int w2, const uint32_t* in2, uint32_t* out2, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * lbs: skeleton solve and linear blend skinning, forward and backward (csrc/lbs.hip).  Replaces the reference's per-frame
