@@ -13,6 +13,7 @@
     dropin.patch_env_driver()     # optional: EnvSpinDecorator.forward's per-frame map rotation, light probe and mip scale on the GPU
     dropin.patch_env_prefilter()  # optional: envmap.prefilterEnvmapSG (the pyramid of _set_lightmap) on ONE HIP kernel per level
     dropin.patch_encoder()        # optional: Encoder.forward's texture stack on the fused conv + bias + LeakyReLU operator
+    dropin.patch_view_texture()   # optional: geom.compute_view_texture and its two visibility helpers (run_gen_texmean) on two HIP kernels, no host sync
     dropin.set_environment(decorator, image)   # another environment map for a live EnvSpinDecorator, pyramid built on the GPU
 
 `install()` registers the module names the reference imports for its native code:
@@ -164,6 +165,82 @@ def patch_geometry_ctor(geom_module=None):
 
     geom_module.make_uv_face_index = make_uv_face_index
     geom_module.index_image_impaint = index_image_impaint
+    return geom_module
+
+
+def patch_view_texture(geom_module=None, tex_module=None):
+    """Opt in to the fused camera-to-UV unwrap (goliath_amd.viewtex, csrc/viewtex.hip): rebinds
+    `geom.compute_face_visibility`, `geom.compute_uv_visiblity_face` and `geom.compute_view_texture`
+    (ca_code/utils/geom.py:834-910: two Python loops over the batch with a th.unique and a host sync each, boolean-mask
+    gathers and scatters) to wrappers that run viewtex for CUDA inputs with a float32 image / float32 vertices; everything
+    else goes to the original, kept on the wrapper as `.reference`.  If `ca_code.utils.tex` is already imported (or is
+    passed in) its by-name import `compute_view_texture` and its `get_tex_rl` (tex.py:21-63) are rebound too; this patch
+    does not import it (it pulls in drtk and cv2).  Implies no other patch; idempotent.  Returns the patched geom module."""
+    from . import viewtex
+
+    if geom_module is None:
+        import ca_code.utils.geom as geom_module
+    if tex_module is None:
+        tex_module = sys.modules.get("ca_code.utils.tex")
+    import torch
+
+    def on_gpu(*tensors):
+        return all(torch.is_tensor(t) and t.is_cuda for t in tensors)
+
+    def wrap(module, name, make):
+        original = getattr(module, name)
+        if getattr(original, "_goliath_viewtex", False):
+            return original
+        fn = make(original)
+        fn.__name__ = name
+        fn.reference = original
+        fn._goliath_viewtex = True
+        setattr(module, name, fn)
+        return fn
+
+    def make_face_visibility(original):
+        def compute_face_visibility(index_img, faces):
+            if on_gpu(index_img) and index_img.dtype in (torch.int32, torch.int64):
+                return viewtex.face_visibility(index_img, faces.shape[0])
+            return original(index_img, faces)
+        return compute_face_visibility
+
+    def make_uv_visibility(original):
+        def compute_uv_visiblity_face(face_index_image, faces, face_index_uv):
+            if on_gpu(face_index_image, face_index_uv) and face_index_image.dtype in (torch.int32, torch.int64):
+                return viewtex.uv_visibility(face_index_image, faces.shape[0], face_index_uv)
+            return original(face_index_image, faces, face_index_uv)
+        return compute_uv_visiblity_face
+
+    def make_view_texture(original):
+        def compute_view_texture(verts, faces, image, face_index_image, normal_image, K, Rt, index_image_uv, bary_image_uv,
+                                 face_index_uv, intensity_threshold=None, normal_threshold=None):
+            if (on_gpu(verts, image, face_index_image, K, Rt, index_image_uv, bary_image_uv, face_index_uv)
+                    and image.dtype == torch.float32 and verts.dtype == torch.float32):
+                return viewtex.compute_view_texture(verts, faces, image, face_index_image, normal_image, K, Rt,
+                                                    index_image_uv, bary_image_uv, face_index_uv,
+                                                    intensity_threshold=intensity_threshold,
+                                                    normal_threshold=normal_threshold)
+            return original(verts, faces, image, face_index_image, normal_image, K, Rt, index_image_uv, bary_image_uv,
+                            face_index_uv, intensity_threshold=intensity_threshold, normal_threshold=normal_threshold)
+        return compute_view_texture
+
+    def make_get_tex_rl(original):
+        def get_tex_rl(rl, image, ply, extrin, intrin, face_index, index_image, bary_image):
+            if (on_gpu(image, ply[0], extrin, intrin, face_index, index_image, bary_image)
+                    and image.dtype == torch.float32 and ply[0].dtype == torch.float32):
+                return viewtex.get_tex_rl(rl, image, ply, extrin, intrin, face_index, index_image, bary_image)
+            return original(rl, image, ply, extrin, intrin, face_index, index_image, bary_image)
+        return get_tex_rl
+
+    wrap(geom_module, "compute_face_visibility", make_face_visibility)
+    wrap(geom_module, "compute_uv_visiblity_face", make_uv_visibility)
+    cvt = wrap(geom_module, "compute_view_texture", make_view_texture)
+    if tex_module is not None:
+        if hasattr(tex_module, "compute_view_texture"):
+            tex_module.compute_view_texture = cvt
+        if hasattr(tex_module, "get_tex_rl"):
+            wrap(tex_module, "get_tex_rl", make_get_tex_rl)
     return geom_module
 
 

@@ -777,6 +777,45 @@ int gol_impaint_gather(int64_t P, const int32_t* src, int w0, const uint32_t* in
                        const uint32_t* in1, uint32_t* out1, int w2, const uint32_t* in2, uint32_t* out2, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * viewtex: camera images unwrapped into UV space and their mean over many views (csrc/viewtex.hip): the per-camera body
+ * of ca_code/scripts/run_gen_texmean.py:83-108 through ca_code/utils/tex.py:21-63.  Forward only, no atomics, no host
+ * sync, bitwise reproducible.
+ * gol_face_visibility: compute_face_visibility (ca_code/utils/geom.py:834-845) without its per-view th.unique:
+ *   index_img[B,H,W] int32 (-1 = empty) -> face_vis[B,F] bytes, zeroed on the stream first, then 1 for every face index
+ *   found in view b.  An index outside [-1, F) is IGNORED (the reference's indexed write would raise).
+ * gol_view_texture: compute_uv_visiblity_face + compute_view_texture (geom.py:847-910) for B views at once.
+ *   verts: view b's [V,3] at verts + b * verts_bstride floats (0 = one posed mesh seen by B cameras); image[B,3,H,W];
+ *   K[B,3,3]; Rt[B,3,4]; index_image_uv[S_h,S_w,3] int32, bary_image_uv[S_h,S_w,3], face_index_uv[S_h,S_w] int32 (-1 =
+ *   empty; ids outside the mesh count as -1); face_vis[B,F] from gol_face_visibility.  Per view and texel, in fp32 in the
+ *   reference's order: xyz = sum_k verts[idx_k] bary_k; p = K (R xyz + t) with the full 3x3 K; pix = p.xy / p.z;
+ *   g = 2 (pix / (W, H)) - 1; grid_sample(nearest, align_corners=False, border): ((g + 1) size - 1) / 2 clamped to
+ *   [0, size - 1], rounded to nearest even; value = (index_image_uv[..., 0] != -1 ? rgb : 0) * vis with
+ *   vis = face_index_uv != -1 && face_vis[b, face_index_uv]; with has_threshold != 0 the value is multiplied by
+ *   all_c(value_c <= intensity_threshold) (geom.py:907-908).
+ *   With mask as the only output (compute_uv_visiblity_face alone) everything but face_index_uv and face_vis may be NULL.
+ *   Outputs, any subset (NULL = not wanted; total and cnt go together):
+ *     tex[B,3,S_h,S_w], mask[B,1,S_h,S_w] bytes 0 / 1 (= vis): every element written;
+ *     total[3,S_h,S_w] += sum_b tex_b and cnt[S_h,S_w] += sum_b vis_b: the sums are formed in view order starting from
+ *     the value found in the accumulator -- bit-identical to B successive `tex_total += tex; tex_cnt += mask`
+ *     (run_gen_texmean.py:102-103).
+ *   STATED: only the face index image decides visibility: a sample behind the camera (p.z < 0) is taken like any other
+ *   (the reference has no depth test).  p.z == 0 or a non-finite pixel coordinate gives the texel 0 for that view (the
+ *   reference's result there is unspecified).  A texel that is not visible gives exactly 0 even where the image holds
+ *   NaN (the reference: NaN * 0 = NaN).  The reference's normal_image / normal_threshold are unused there and have no
+ *   counterpart here.
+ * gol_texmean_finalize: out[S_h,S_w,3] = total / (cnt + eps) (run_gen_texmean.py:105-106); flip_rows != 0 mirrors the
+ *   rows, bgr != 0 swaps the channels to BGR (:106-108, up to the cv2.imwrite).  Out of place.
+ * ---------------------------------------------------------------------------------------- */
+int gol_face_visibility(int B, int F, int H, int W, const int32_t* index_img, uint8_t* face_vis, void* stream);
+int gol_view_texture(int B, int V, int F, int H, int W, int S_h, int S_w, const float* verts, int64_t verts_bstride,
+                     const float* image, const float* K, const float* Rt, const int32_t* index_image_uv,
+                     const float* bary_image_uv, const int32_t* face_index_uv, const uint8_t* face_vis,
+                     int has_threshold, float intensity_threshold, float* tex, uint8_t* mask, float* total, float* cnt,
+                     void* stream);
+int gol_texmean_finalize(int S_h, int S_w, const float* total, const float* cnt, float eps, int flip_rows, int bgr,
+                         float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * lbs: skeleton solve and linear blend skinning, forward and backward (csrc/lbs.hip).  Replaces the reference's per-frame
  * PyTorch of ca_code/utils/lbs.py as called by URHand (ca_code/models/urhand.py:767) and hand_mvp / hand_teacher_mvp
  * (ca_code/models/hand_mvp.py:390).  The constants are packed once by goliath_amd.lbs.Skeleton (int32 unless stated):
