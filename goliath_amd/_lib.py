@@ -38,6 +38,7 @@ _SYMBOLS = [
     "gol_enc_conv_fwd", "gol_enc_conv_bwd_scratch_floats", "gol_enc_conv_bwd",
     "gol_mesh_raster_flat", "gol_uv_face_index_workspace_bytes", "gol_uv_face_index", "gol_uv_topology", "gol_nearest_valid", "gol_impaint_gather",
     "gol_face_visibility", "gol_view_texture", "gol_texmean_finalize",
+    "gol_uvframes_bwd_scratch_floats", "gol_uvframes_fwd", "gol_uvframes_bwd",
 ]
 
 

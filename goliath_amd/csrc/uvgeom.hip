@@ -33,22 +33,6 @@ constexpr int kItemRow = 16;        // lanes per item (one DPP row)
 
 using namespace gol_vec3;
 
-// gradient of x / max(|x|, eps) for upstream g
-__device__ __forceinline__ V3 normalize_bwd(V3 x, V3 g, float eps) {
-  const float n = norm(x);
-  if (n >= eps) {
-    const V3 u = x / n;
-    return (g - u * dot(u, g)) / n;
-  }
-  return g / eps;
-}
-
-// the three ids of row `r` of an [N,3] table, validated against [0, V): false = treat as absent
-__device__ __forceinline__ bool ids3(const int32_t* __restrict__ tab, int r, int V, int& a, int& b, int& c) {
-  a = tab[3 * r]; b = tab[3 * r + 1]; c = tab[3 * r + 2];
-  return (unsigned)a < (unsigned)V && (unsigned)b < (unsigned)V && (unsigned)c < (unsigned)V;
-}
-
 // sum over the faces of vertex v of cross / max(|cross|, 1e-5), in slot (= face) order -- the order scatter_add_ visits
 __device__ __forceinline__ V3 vertex_normal_sum(const float* __restrict__ vb, const int32_t* __restrict__ vi,
                                                 const int32_t* __restrict__ vf_start,

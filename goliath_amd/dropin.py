@@ -599,7 +599,7 @@ def patch_image_ops(*modules):
     return done
 
 
-def patch_urhand(urhand_module=None, mesh_render_layer=False):
+def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False):
     """BASELINE config 4 as a drop-in: `ConvTeacherDecoder.forward` (ca_code/models/urhand.py:349-630) with its two light
     loops and both shadow-map evaluations on the HIP kernels (goliath_amd.urhand.conv_teacher_decoder_forward) and the
     stand-alone shadow-map lookup (`get_shadow_map`, imported at urhand.py:44).  The depth images of the light cameras are
@@ -611,7 +611,16 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False):
     edge_grad=self.training) -- with drtk installed that stays drtk's.  mesh_render_layer=True rebinds it to
     goliath_amd.meshraster.RenderLayer (a stack without drtk): same constructor / forward / output dict, differentiable
     w.r.t. texture and vertices incl. an edge-gradient estimator (round 4) whose conventions are stated and checked against
-    a supersampled render, not against drtk (absent: parity unpinned).  Returns the patched module."""
+    a supersampled render, not against drtk (absent: parity unpinned).
+
+    uv_frames=True installs goliath_amd.urhand.conv_teacher_decoder_forward_uv_frames instead: the same forward with the TBN
+    frames of both passes (urhand.py:366-392, :467-486), the two normal maps and the view conditioning (:573-578) on the
+    fused operator of goliath_amd.uvframes (gol_uvframes_fwd / _bwd: no [B,S,S,3,3] image, no boolean-mask gather, no host
+    sync).  Its topology is packed on first use from the decoder's `geo_fn` buffers (vi, vt, v2uv, index_image,
+    face_index_image, bary_image) and cached on the decoder.  Opt-in: the default binding is unchanged.  What it gains
+    against the lines it replaces, per batch size and direction, is measured by tools/uvframes_probe.py
+    (profiles/uvframes_probe.json, DESIGN.md section 8 "uvframes"); a row in which the fused path is not faster beyond the
+    parent's own run-to-run spread is named there.  Returns the patched module."""
     from . import meshraster, shadowmap, urhand
 
     if urhand_module is None:
@@ -634,7 +643,8 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False):
                       "drtk is absent in this build, so their parity with drtk.edge_grad_estimator is UNVERIFIED; "
                       "meshraster.EDGE_STATS (opt-in: GOLIATH_EDGE_STATS=1) counts the discontinuities that receive no gradient", RuntimeWarning, stacklevel=2)
         urhand_module.RenderLayer = meshraster.RenderLayer
-    urhand_module.ConvTeacherDecoder.forward = urhand.conv_teacher_decoder_forward
+    urhand_module.ConvTeacherDecoder.forward = (urhand.conv_teacher_decoder_forward_uv_frames if uv_frames
+                                                else urhand.conv_teacher_decoder_forward)
     return urhand_module
 
 

@@ -8,6 +8,9 @@
         * GGX / Schlick light loop + physical texture (:508-567) -> gol_uvlight_ggx_fwd/bwd
       nothing of size [B,L,3,S,S] is materialised; everything else (TBN frames, the displacement / texture UNets, the
       view conditioning) is the decoder's own PyTorch sub-modules, called exactly as the reference calls them.
+    conv_teacher_decoder_forward_uv_frames   the same, with
+        * the TBN frames of both passes, the two normal maps and the view conditioning (:366-392, :467-486, :573-578)
+                                                          -> gol_uvframes_fwd/bwd (goliath_amd.uvframes), opt-in
     olat_rgb_decoder_forward_rgb   <- /root/reference/ca_code/models/hand_teacher_mvp.py:253-494
         * the deep-shadow march (:271-358: L-fold copies of the primitive set and of a 4-channel template, an ordinary
           ray march with with_shadow=True) -> gol_mvp_shadow_march (all lights of a frame share transforms, tree and an
@@ -24,7 +27,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from . import meshraster, mvp, mvpprims, shadowmap, uvlight
+from . import meshraster, mvp, mvpprims, shadowmap, uvframes, uvlight
 
 
 def _home(obj):
@@ -103,15 +106,46 @@ def conv_teacher_decoder_forward(
     iteration: Optional[int] = None,
 ):
     """Drop-in for ConvTeacherDecoder.forward (urhand.py:349-630): same arguments, same output dict."""
+    return _decoder_forward(self, False, lbs_motion, id_mesh, tex_mean, verts_rec, cam_pos, light_pos, light_intensity)
+
+
+def conv_teacher_decoder_forward_uv_frames(
+    self,
+    lbs_motion,
+    id_mesh,
+    tex_mean,
+    verts_rec,
+    cam_pos,
+    light_pos,
+    light_intensity,
+    seam_sampler = None,
+    ccm = None,
+    falloff_dist = None,
+    nearfield = False,
+    iteration: Optional[int] = None,
+):
+    """conv_teacher_decoder_forward with both TBN passes, the two normal maps and the view conditioning on the fused
+    operator of goliath_amd.uvframes (gol_uvframes_fwd / _bwd): no [B,S,S,3,3] frame image, no boolean-mask gather, no host
+    sync.  Opt-in through dropin.patch_urhand(uv_frames=True).  Measured against the lines it replaces in
+    profiles/uvframes_probe.json ("uvframes")."""
+    return _decoder_forward(self, True, lbs_motion, id_mesh, tex_mean, verts_rec, cam_pos, light_pos, light_intensity)
+
+
+def _decoder_forward(self, fused_frames, lbs_motion, id_mesh, tex_mean, verts_rec, cam_pos, light_pos, light_intensity):
     mod = _home(self)
     gf = self.geo_fn
     B = verts_rec.shape[0]
     # ---- pass 1 on the LBS surface: Lambert + Phong features (urhand.py:366-445) ----
-    frames, mask = _uv_frames(self, mod, verts_rec)
+    if fused_frames:
+        topo = uvframes.topology_of(self)
+        nml = uvframes.uv_frames(verts_rec, topo)[0]
+    else:
+        frames, mask = _uv_frames(self, mod, verts_rec)
     p_uv = gf.to_uv(verts_rec)
     if not self.impaint_uv:
         vert_mask = (verts_rec.detach() - gf.from_uv(p_uv).detach()).abs() > 1
-    nml = _normal_map(frames)
+    if not fused_frames:
+        nml = _normal_map(frames)
     shadow_map = shadow_maps(self.rl, mod, verts_rec, p_uv, nml, light_pos) if self.shadow else None
     diff_raw, spec_raw = uvlight.phong_features(p_uv, nml, cam_pos, light_pos, light_intensity, shadow_map,
                                                 self.spec_powers)
@@ -142,9 +176,13 @@ def conv_teacher_decoder_forward(
     if not self.impaint_uv:
         verts_displaced[vert_mask] = verts_rec[vert_mask]
     # ---- pass 2 on the displaced surface: GGX features + physically based texture (urhand.py:469-571) ----
-    frames, _ = _uv_frames(self, mod, verts_displaced, normals_from=p_uv, flip_normal=True)
-    nml = _normal_map(frames)
-    v_uv = F.normalize(cam_pos[..., None, None] - p_uv, dim=1)
+    if fused_frames:
+        nml, viewout, _ = uvframes.uv_frames(verts_displaced, topo, posmap=p_uv, flip_normal=True,
+                                             cam_pos=cam_pos if self.view_cond else None)
+    else:
+        frames, _ = _uv_frames(self, mod, verts_displaced, normals_from=p_uv, flip_normal=True)
+        nml = _normal_map(frames)
+        v_uv = F.normalize(cam_pos[..., None, None] - p_uv, dim=1)
     if self.shadow:
         shadow_map = shadow_maps(self.rl, mod, verts_displaced, p_uv, nml, light_pos)
     if self.scaled_albedo:
@@ -154,8 +192,9 @@ def conv_teacher_decoder_forward(
     outputs.update(phys_tex=rgb_phys * (torch.sigmoid(self.global_scale) / 2.0 + 0.3), roughness=roughness)
     # ---- view conditioning + texture decoder (urhand.py:573-620), the decoder's own sub-modules ----
     if self.view_cond:
-        viewout = v_uv.permute(0, 2, 3, 1)[:, :, :, None, :] @ frames.transpose(-2, -1)
-        viewout = viewout[:, :, :, 0, :].permute(0, 3, 1, 2)
+        if not fused_frames:
+            viewout = v_uv.permute(0, 2, 3, 1)[:, :, :, None, :] @ frames.transpose(-2, -1)
+            viewout = viewout[:, :, :, 0, :].permute(0, 3, 1, 2)
         viewout = F.interpolate(viewout, (id_pose_feat.shape[2:]), mode="bilinear")
         id_pose_feat = torch.cat([id_pose_feat, viewout], dim=1)
     outputs.update(id_pose_conv=id_pose_feat)

@@ -743,6 +743,49 @@ int gol_uvgeom_bwd(int B, int V, int F, int S, int T, int I, const float* verts,
                    const float* g_tn, float* item_sums, float* g_s, float* g_verts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * uvframes: URHand's per-texel tangent frames, normal map and view conditioning, forward and backward
+ * (csrc/uvframes.hip).  Replaces, in ConvTeacherDecoder.forward, ca_code/models/urhand.py:366-392 (pass 1), :467-486
+ * (pass 2) and :573-578 (view conditioning) with the helpers they call: compute_tbn_uv_given_normal
+ * (ca_code/utils/geom.py:432-470), xyz2normals (geom.py:665-686), vert_normals (geom.py:337-346).  On top of uvgeom's
+ * arrays for index_image (texel_rec, triples, item_start, texel_of) goliath_amd.uvframes.UVFramesTopology packs:
+ *   tri_const[T,4] float: (f, vt01.y, vt02.y, 0) of tri_uv = vt[v2uv[triple, 0]] (urhand.py:369: the FIRST uv slot of a
+ *     vertex), fin = vt01.x vt02.y - vt01.y vt02.x, |fin| < 1e-8 -> +1e-8, f = 1 / fin (geom.py:451-454), in float32;
+ *   tri_item_start[T+1]: a triple's run of items; vq_start[V+1], vq_slot[3T]: vertex -> (triple, corner), slot = 3 t + k;
+ *   ntexel_rec, ntriples, nitem_start, ntexel_of, nvt_start, nvt_slot (Tn triples, In items): uvgeom's arrays for the
+ *     image vi[face_index_image], the vertex triple mode 0 interpolates normals over (urhand.py:377).
+ * Per (view, triple): t0 = raw / max(|raw|, 1e-5), raw = f (v01 vt02.y - v02 vt01.y) (geom.py:456-459).
+ * Per (view, covered texel): the normal n,
+ *   mode 0 (urhand.py:375-383): n = x / max(|x|, 1e-5), x = sum_k bary_k vn[ntriple_k], vn = gol_vert_normals_fwd(eps 1e-5);
+ *   mode 1 (urhand.py:467-468): n = c / max(|c|, 1e-8), c = U x V, U = (p[r+1,c] - p[r-1,c]) / -2,
+ *           V = (p[r,c+1] - p[r,c-1]) / -2 on posmap, zeros beyond the map, neighbours read whether covered or not;
+ *   b = n x t0, b /= max(|b|, 1e-5); t = b x n, t /= max(|t|, 1e-5) (geom.py:462-469); rows (t, -b, s n), s = -1 with
+ *   flip_normal (urhand.py:385-392, :479-486).  v = d / max(|d|, 1e-12), d = cam_pos - posmap (urhand.py:573).
+ * gol_uvframes_fwd writes every element of nml[B,3,S,S] = row 2, of viewout[B,3,S,S] = rows . v (NULL = not wanted; needs
+ *   cam_pos[B,3] and posmap[B,3,S,S]) and of frames[B,S,S,3,3] (NULL = not wanted); zeros where uncovered.  vn[B,V,3]
+ *   (mode 0) and t0[B,T,3] are written for the backward.
+ * gol_uvframes_bwd: g_nml, g_viewout, g_frames (NULL = zero) -> g_verts[B,V,3], g_posmap[B,3,S,S] (mode 1's stencil and
+ *   the view term; NULL allowed in mode 0 without g_cam_pos) and g_cam_pos[B,3] (NULL = not wanted), each fully written.
+ *   scratch: gol_uvframes_bwd_scratch_floats(...) floats, 8-byte aligned.
+ * A norm below its clamp makes the denominator a constant in the derivative, at equality the gradient passes; fin's clamp
+ * is a topology constant.  No atomics: every sum has a fixed order, all outputs are bitwise reproducible.
+ * ---------------------------------------------------------------------------------------- */
+long long gol_uvframes_bwd_scratch_floats(int B, int V, int S, int T, int I, int In, int mode);
+int gol_uvframes_fwd(int B, int V, int F, int S, int T, int Tn, int mode, int flip_normal, const float* verts,
+                     const int32_t* vi, const int32_t* vf_start, const int32_t* vf_slot, const int32_t* texel_rec,
+                     const int32_t* triples, const float* tri_const, const int32_t* ntexel_rec, const int32_t* ntriples,
+                     const float* posmap, const float* cam_pos, float* vn, float* t0, float* nml, float* viewout,
+                     float* frames, void* stream);
+int gol_uvframes_bwd(int B, int V, int F, int S, int T, int Tn, int I, int In, int mode, int flip_normal,
+                     const float* verts, const int32_t* vi, const int32_t* vf_start, const int32_t* vf_slot,
+                     const int32_t* texel_rec, const int32_t* triples, const float* tri_const,
+                     const int32_t* item_start, const int32_t* texel_of, const int32_t* tri_item_start,
+                     const int32_t* vq_start, const int32_t* vq_slot, const int32_t* ntexel_rec, const int32_t* ntriples,
+                     const int32_t* nitem_start, const int32_t* ntexel_of, const int32_t* nvt_start,
+                     const int32_t* nvt_slot, const float* posmap, const float* cam_pos, const float* vn, const float* t0,
+                     const float* g_nml, const float* g_viewout, const float* g_frames, float* scratch, float* g_verts,
+                     float* g_posmap, float* g_cam_pos, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * uvtopo: the constant UV topology images GeometryModule.__init__ registers (ca_code/utils/geom.py:197-249), without
  * pytorch3d and without the KD-tree (csrc/uvtopo.hip).  Built once per model; forward only, no atomics, reproducible.
  * Texel (r, c) of an [H,W] image is sampled at uv = ((c + 0.5) / W, (r + 0.5) / H); flip_uv != 0 mirrors v (1 - v, in
