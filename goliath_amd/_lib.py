@@ -39,6 +39,7 @@ _SYMBOLS = [
     "gol_mesh_raster_flat", "gol_uv_face_index_workspace_bytes", "gol_uv_face_index", "gol_uv_topology", "gol_nearest_valid", "gol_impaint_gather",
     "gol_face_visibility", "gol_view_texture", "gol_texmean_finalize",
     "gol_uvframes_bwd_scratch_floats", "gol_uvframes_fwd", "gol_uvframes_bwd",
+    "gol_upconv_fwd", "gol_upconv_bwd_scratch_floats", "gol_upconv_bwd",
 ]
 
 

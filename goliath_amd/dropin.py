@@ -599,7 +599,7 @@ def patch_image_ops(*modules):
     return done
 
 
-def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False):
+def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, texture_decoder=False):
     """BASELINE config 4 as a drop-in: `ConvTeacherDecoder.forward` (ca_code/models/urhand.py:349-630) with its two light
     loops and both shadow-map evaluations on the HIP kernels (goliath_amd.urhand.conv_teacher_decoder_forward) and the
     stand-alone shadow-map lookup (`get_shadow_map`, imported at urhand.py:44).  The depth images of the light cameras are
@@ -620,8 +620,17 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False):
     face_index_image, bary_image) and cached on the decoder.  Opt-in: the default binding is unchanged.  What it gains
     against the lines it replaces, per batch size and direction, is measured by tools/uvframes_probe.py
     (profiles/uvframes_probe.json, DESIGN.md section 8 "uvframes"); a row in which the fused path is not faster beyond the
-    parent's own run-to-run spread is named there.  Returns the patched module."""
-    from . import meshraster, shadowmap, urhand
+    parent's own run-to-run spread is named there.
+
+    texture_decoder=True sets `texdec.TEXTURE_DECODER_FLAG` on the decoder class: either forward then runs its two texture
+    branches (urhand.py:583-608) through goliath_amd.texdec.texture_branches, which hands a layer -- exact 2x bilinear
+    resize + weight-normalised 3x3 convolution + bias / LeakyReLU or gate / gainbias -- to the fused operator
+    (gol_upconv_fwd / _bwd: the upsampled tensor never exists in memory) where its shape is in texdec.DISPATCH, and runs
+    the reference's three lines everywhere else (plain nn.Conv2d layers, CPU tensors, inputs that are not half the target
+    size, shapes that lost the probe).  Opt-in: the default binding clears the flag and is unchanged.  The measured gain per
+    layer shape is written by tools/texdec_probe.py to profiles/texdec_probe.json.  Returns the
+    patched module."""
+    from . import meshraster, shadowmap, texdec, urhand
 
     if urhand_module is None:
         import ca_code.models.urhand as urhand_module
@@ -645,6 +654,7 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False):
         urhand_module.RenderLayer = meshraster.RenderLayer
     urhand_module.ConvTeacherDecoder.forward = (urhand.conv_teacher_decoder_forward_uv_frames if uv_frames
                                                 else urhand.conv_teacher_decoder_forward)
+    setattr(urhand_module.ConvTeacherDecoder, texdec.TEXTURE_DECODER_FLAG, bool(texture_decoder))
     return urhand_module
 
 

@@ -11,6 +11,9 @@
     conv_teacher_decoder_forward_uv_frames   the same, with
         * the TBN frames of both passes, the two normal maps and the view conditioning (:366-392, :467-486, :573-578)
                                                           -> gol_uvframes_fwd/bwd (goliath_amd.uvframes), opt-in
+    either forward, where the decoder class carries texdec.TEXTURE_DECODER_FLAG (dropin.patch_urhand(texture_decoder=True)):
+        * the two 7-layer texture branches (:583-608): 2x bilinear resize + weight-normalised 3x3 conv + bias / LeakyReLU
+          or gate / gainbias per layer               -> gol_upconv_fwd/bwd (goliath_amd.texdec), per shape, opt-in
     olat_rgb_decoder_forward_rgb   <- /root/reference/ca_code/models/hand_teacher_mvp.py:253-494
         * the deep-shadow march (:271-358: L-fold copies of the primitive set and of a 4-channel template, an ordinary
           ray march with with_shadow=True) -> gol_mvp_shadow_march (all lights of a frame share transforms, tree and an
@@ -27,7 +30,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from . import meshraster, mvp, mvpprims, shadowmap, uvframes, uvlight
+from . import meshraster, mvp, mvpprims, shadowmap, texdec, uvframes, uvlight
 
 
 def _home(obj):
@@ -200,19 +203,22 @@ def _decoder_forward(self, fused_frames, lbs_motion, id_mesh, tex_mean, verts_re
     outputs.update(id_pose_conv=id_pose_feat)
     joint_feat = self.joint_conv_block_tex(id_pose_feat)
     z, gainbias = self.featenc(feat_p.detach().reshape(B, -1, feat_p.shape[-2], feat_p.shape[-1]))
-    acts, x, hh = [], joint_feat, 64
-    for i in range(self.n_layers_tex):                   # non-linear branch
-        x = F.interpolate(x, (hh, hh), mode="bilinear", align_corners=True)
-        x = F.leaky_relu(self.texmod0[i](x), 0.2)
-        acts.append(x)
-        hh *= 2
-    x, hh = z, 64
-    for i in range(self.n_layers_tex):                   # energy-in / energy-out linear branch, gated by the activations
-        x = F.interpolate(x, (hh, hh), mode="bilinear", align_corners=True)
-        x = self.texmod1[i](x) * acts[i]
-        hh *= 2
-        if i < len(gainbias):
-            x = (x + gainbias[i]) * 0.707107
+    if getattr(type(self), texdec.TEXTURE_DECODER_FLAG, False):   # dropin.patch_urhand(texture_decoder=True)
+        x = texdec.texture_branches(self, joint_feat, z, gainbias)
+    else:
+        acts, x, hh = [], joint_feat, 64
+        for i in range(self.n_layers_tex):               # non-linear branch
+            x = F.interpolate(x, (hh, hh), mode="bilinear", align_corners=True)
+            x = F.leaky_relu(self.texmod0[i](x), 0.2)
+            acts.append(x)
+            hh *= 2
+        x, hh = z, 64
+        for i in range(self.n_layers_tex):               # energy-in / energy-out linear branch, gated by the activations
+            x = F.interpolate(x, (hh, hh), mode="bilinear", align_corners=True)
+            x = self.texmod1[i](x) * acts[i]
+            hh *= 2
+            if i < len(gainbias):
+                x = (x + gainbias[i]) * 0.707107
     rgb = F.interpolate(x, (gf.uv_size, gf.uv_size), mode="bilinear", align_corners=True)
     if self.shadow and not self.training:                # "for better shadow generalization" (urhand.py:611-613)
         rgb = rgb * ((lint / lint_scale[:, None]) * shadow_map).sum(1)

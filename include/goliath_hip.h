@@ -588,6 +588,40 @@ int gol_enc_conv_bwd(int B, int Ci, int Co, int H, int W, float leak, float in_s
                      float* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Texture-decoder layer of URHand as one operator: exact 2x bilinear resize (align_corners=True) + weight-normalised
+ * 3x3 / stride 1 / pad 1 convolution + epilogue.  Replaces, per layer of the two texture branches of
+ * ConvTeacherDecoder.forward (ca_code/models/urhand.py:583-608; layers built at :302-323 from la.Conv2dWNUB(.., 3, 1, 1)
+ * and la.Conv2dWN(.., 3, 1, 1, bias=False), ca_code/nn/layers.py:276-328, weight norm layers.py:157-244),
+ *   F.interpolate(x, (2 Hi, 2 Wi), mode="bilinear", align_corners=True), the MIOpen convolution and
+ *   mode 0 (texmod0, urhand.py:592-597): the ATen add of the untied bias and leaky_relu,
+ *   mode 1 (texmod1, urhand.py:600-606): the ATen multiply by the other branch's activation, add of gainbias, * 0.707107:
+ *   U[b,ci,r,c]   = bilinear(x[b,ci]) at (r (Hi-1)/(H-1), c (Wi-1)/(W-1)), H = 2 Hi, W = 2 Wi, by the integer-ratio rule
+ *                   r0 = (r (Hi-1)) div (H-1), frac = float((r (Hi-1)) mod (H-1)) / float(H-1), r1 = min(r0+1, Hi-1)
+ *                   (same per column): pinned against float64, not against the library's fp32 `dst * scale`
+ *   acc[b,co,r,c] = sum_{ci,ky,kx} Upad[b,ci,r-1+ky,c-1+kx] w_eff[co,ci,ky,kx]     (Upad = U inside the image, 0 outside)
+ *   mode 0:  y = lrelu(acc + bias[co,r,c], leak), leak > 0
+ *   mode 1:  y = (acc * gate[b,co,r,c] + gb[b,co,r,c]) * scale                      (gb may be NULL: no add)
+ *   x [B,Ci,Hi,Wi]; w_eff [Co,Ci,3,3] (the weight norm already applied, goliath_amd/tail.py:wn_weight); bias [Co,H,W];
+ *   gate, gb, y [B,Co,H,W].  fp32 MFMA, exact fp32.  U never exists in memory; nothing but y is written.
+ * Ci must be a multiple of 8 and Co a multiple of 16 or one of 1..4 (zero weight rows), otherwise GOL_ERR_UNSUPPORTED.
+ * bwd forms g_pre = g_y * (y > 0 ? 1 : leak) (mode 0; needs y) or scale * gate * g_y (mode 1; needs gate) while loading;
+ * any of the outputs may be NULL = not wanted, at no cost:
+ *   g_x [B,Ci,Hi,Wi] written: the bilinear adjoint of the transposed convolution of g_pre, gathered per source texel from
+ *       a region of g_U kept on chip (no atomics); needs w_eff;
+ *   g_w [Co,Ci,3,3] written (= sum_{b,r,c} g_pre Upad, U recomputed from x); needs x and
+ *       scratch[gol_upconv_bwd_scratch_floats] (per-workgroup partial sums added in a fixed order by a second kernel: no
+ *       float atomics, bitwise reproducible);
+ *   mode 0: g_bias [Co,H,W] written (= sum_b g_pre);
+ *   mode 1: g_gate [B,Co,H,W] = scale * g_y * acc (acc recomputed: needs x and w_eff) and g_gb [B,Co,H,W] = scale * g_y.
+ * ---------------------------------------------------------------------------------------- */
+int gol_upconv_fwd(int B, int Ci, int Co, int Hi, int Wi, int mode, float leak, float scale, const float* x,
+                   const float* w_eff, const float* bias, const float* gate, const float* gb, float* y, void* stream);
+long long gol_upconv_bwd_scratch_floats(int B, int Ci, int Co, int Hi, int Wi);
+int gol_upconv_bwd(int B, int Ci, int Co, int Hi, int Wi, int mode, float leak, float scale, const float* x,
+                   const float* w_eff, const float* y, const float* gate, const float* g_y, float* g_x, float* g_w,
+                   float* g_bias, float* g_gate, float* g_gb, float* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * SSIM image loss ("next" row).  Replaces `ssim` / `_ssim`
  * (ca_code/utils/ssim.py:25-65) as used by rgb_ssim (ca_code/loss/__init__.py:478-494): 11x11 Gaussian
  * window (sigma 1.5, zero padding), C1 = 0.01^2, C2 = 0.03^2, masked mean.
