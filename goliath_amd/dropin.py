@@ -599,7 +599,7 @@ def patch_image_ops(*modules):
     return done
 
 
-def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, texture_decoder=False):
+def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, texture_decoder=False, texture_tail=False):
     """BASELINE config 4 as a drop-in: `ConvTeacherDecoder.forward` (ca_code/models/urhand.py:349-630) with its two light
     loops and both shadow-map evaluations on the HIP kernels (goliath_amd.urhand.conv_teacher_decoder_forward) and the
     stand-alone shadow-map lookup (`get_shadow_map`, imported at urhand.py:44).  The depth images of the light cameras are
@@ -628,9 +628,18 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, t
     (gol_upconv_fwd / _bwd: the upsampled tensor never exists in memory) where its shape is in texdec.DISPATCH, and runs
     the reference's three lines everywhere else (plain nn.Conv2d layers, CPU tensors, inputs that are not half the target
     size, shapes that lost the probe).  Opt-in: the default binding clears the flag and is unchanged.  The measured gain per
-    layer shape is written by tools/texdec_probe.py to profiles/texdec_probe.json.  Returns the
-    patched module."""
-    from . import meshraster, shadowmap, texdec, urhand
+    layer shape is written by tools/texdec_probe.py to profiles/texdec_probe.json.
+
+    texture_tail=True rebinds `AutoEncoder.forward` (urhand.py:750-990) to goliath_amd.urhand.autoencoder_forward -- the same
+    parameter list, the same `preds` keys -- and sets `uvtex.TEXTURE_TAIL_FLAG` on the class: the stretch from the decoder's
+    relight_preds["tex"] to the RGBA textures the renderer takes (gain / bias, CalV5, clamp, seam resample, alpha packing,
+    phys_tex packing, the two normal-colour textures: urhand.py:721-747, :788-790, :805-807, :824-832, :843-847) then runs
+    on goliath_amd.uvtex (gol_uvtex_fwd / _bwd, gol_pack_rgba_*, gol_normal_rgba: one pass each way, no host sync per view,
+    a deterministic seam backward).  The seam tap list is packed on first use from `seam_sampler.uvs` / `.weights` and
+    cached on the sampler.  Opt-in: the default leaves `AutoEncoder.forward` untouched (and puts the original back after
+    an earlier texture_tail=True).  Measured by tools/uvtex_probe.py (profiles/uvtex_probe.json, DESIGN.md section 8
+    "uvtex").  Returns the patched module."""
+    from . import meshraster, shadowmap, texdec, urhand, uvtex
 
     if urhand_module is None:
         import ca_code.models.urhand as urhand_module
@@ -655,6 +664,16 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, t
     urhand_module.ConvTeacherDecoder.forward = (urhand.conv_teacher_decoder_forward_uv_frames if uv_frames
                                                 else urhand.conv_teacher_decoder_forward)
     setattr(urhand_module.ConvTeacherDecoder, texdec.TEXTURE_DECODER_FLAG, bool(texture_decoder))
+    ae = urhand_module.AutoEncoder if texture_tail else getattr(urhand_module, "AutoEncoder", None)
+    if texture_tail:
+        if "_gol_reference_forward" not in ae.__dict__:
+            ae._gol_reference_forward = ae.__dict__["forward"]
+        ae.forward = urhand.autoencoder_forward
+        setattr(ae, uvtex.TEXTURE_TAIL_FLAG, True)
+    elif ae is not None and "_gol_reference_forward" in ae.__dict__:   # undo an earlier texture_tail=True
+        ae.forward = ae.__dict__["_gol_reference_forward"]
+        del ae._gol_reference_forward
+        setattr(ae, uvtex.TEXTURE_TAIL_FLAG, False)
     return urhand_module
 
 

@@ -19,18 +19,27 @@
           ray march with with_shadow=True) -> gol_mvp_shadow_march (all lights of a frame share transforms, tree and an
           alpha-only template)
 
+    autoencoder_forward   <- /root/reference/ca_code/models/urhand.py:750-990 (AutoEncoder.forward with forward_tex,
+        :711-748); where the model's class carries uvtex.TEXTURE_TAIL_FLAG (dropin.patch_urhand(texture_tail=True)):
+        * gain / bias, CalV5, clamp, seam resample and alpha packing (:721-747, :805-807, :824-825)
+                                                          -> gol_uvtex_fwd/bwd (goliath_amd.uvtex.texture_tail)
+        * phys_tex * 255, clamp, alpha (:788-790, :826)   -> gol_pack_rgba_fwd/bwd
+        * the two normal-colour textures (:828-832, :843-847) -> gol_normal_rgba
+      without the flag the same lines run as torch operators (also on the CPU).
+
 Both are installed by `goliath_amd.dropin.patch_urhand()` / `patch_hand_teacher()` as methods of the reference classes
 (same parameter lists: tests/test_dropin_real_classes.py).  The geometry helpers they call (`vert_normals`,
 `compute_tbn_uv_given_normal`, `xyz2normals`, `tile2d`, `index`, `build_cam_rot_mat`) are looked up in the module that
 defines the decoder class -- for the reference that is ca_code.models.urhand / hand_teacher_mvp themselves.
 """
 import sys
-from typing import Optional
+from typing import List, Optional
 
 import torch
 import torch.nn.functional as F
 
-from . import meshraster, mvp, mvpprims, shadowmap, texdec, uvframes, uvlight
+from . import meshraster, mvp, mvpprims, shadowmap, texdec, uvframes, uvlight, uvtex
+from .imgtail import cal_v5_matrix
 
 
 def _home(obj):
@@ -234,6 +243,189 @@ def _decoder_forward(self, fused_frames, lbs_motion, id_mesh, tex_mean, verts_re
         interm_features2reg=gainbias,
     )
     return outputs
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def _split_gain_bias(tex):
+    """urhand.py:721-729."""
+    C = tex.shape[1]
+    if C == 2:
+        return tex[:, 0:1], tex[:, 1:2]
+    if C == 4:
+        return tex[:, 0:3], tex[:, 3:4]
+    if C == 6:
+        return tex[:, 0:3], tex[:, 3:6]
+    raise ValueError(f"relight_preds['tex'] must have 2, 4 or 6 channels, got {C}")
+
+
+def _interim_images(self, relight_preds, tex_mean):
+    """forward_tex's detached visualisation images (urhand.py:730-740); only the vis_feature renders read them."""
+    gain, bias = _split_gain_bias(relight_preds["tex"])
+    interim = {}
+    if self.decoder_relight.refine_geo:
+        interim["roughness"] = (relight_preds["roughness"].detach() * 255).clamp_(min=0, max=255)
+    interim["tex_mean_vis"] = tex_mean.detach()
+    interim["gain"] = (gain.detach() * 255).clamp_(min=0, max=255)
+    interim["bias"] = (bias.detach() * self.tex_std).clamp_(min=0, max=255)
+    if relight_preds.get("diff_feature") is not None:
+        interim["diffuse_rgb"] = (relight_preds["diff_feature"].detach() * tex_mean.detach()).clamp_(min=0, max=255)
+    interim["tex_ua"] = tex_mean.detach().clamp_(min=0, max=255)
+    return interim
+
+
+def _normal_colours(nml, Rt):
+    """urhand.py:828-832 / :843-847 with the texture size taken from the tensor."""
+    B = nml.shape[0]
+    n = torch.bmm(nml.detach().permute(0, 2, 3, 1).reshape(B, -1, 3), Rt[:, :3, :3].permute(0, 2, 1))
+    n = n.reshape(B, *nml.shape[-2:], 3).permute(0, 3, 1, 2)
+    n = (1 - n) * 127.5
+    return torch.cat([n, torch.ones_like(n[:, :1])], dim=1)
+
+
+def texture_stretch(self, relight_preds, tex_mean, index, Rt, fused, rgba=True):
+    """The stretch of AutoEncoder.forward from relight_preds["tex"] to the four RGBA textures the renderer takes
+    (urhand.py:788-807 with forward_tex :721-747, and :824-832, :843-847; the RGBA textures only with `rgba`):
+    (texrec_before_warp, tex_rec, tex_rgb_seg, phys_tex_rgb_seg, feat_normal_raw, feat_normal).  fused: on goliath_amd.uvtex
+    (tex_rec is then a view of tex_rgb_seg); else the reference's lines as torch operators, on any device.  tex_mean is the
+    forward's local `self.tex_mean.repeat(bs, 1, 1, 1)`; the torch lines clamp it in place as the reference does."""
+    phys_tex = relight_preds.get("phys_tex")
+    tex_rgb_seg = phys_tex_rgb_seg = feat_normal_raw = feat_normal = None
+    if fused:
+        cal_M = cal_b = None
+        if index is not None and hasattr(self, "cal"):
+            cal_M, cal_b = cal_v5_matrix(self.cal, self.cal.name_to_idx(index["camera"]))
+        seams = uvtex.seams_of(self.seam_sampler) if self.impaint_uv else None
+        before, tex_rgb_seg = uvtex.texture_tail(relight_preds["tex"], self.tex_mean, self.tex_std, seams, cal_M, cal_b)
+        tex_rec = tex_rgb_seg[:, :3]
+        if rgba:
+            if phys_tex is not None:
+                phys_tex_rgb_seg = uvtex.pack_rgba(phys_tex, 255.0, 0.0, 255.0)
+            else:
+                phys_tex_rgb_seg = torch.cat([torch.zeros_like(tex_rec), torch.ones_like(tex_rec[:, :1])], dim=1)
+            feat_normal_raw = uvtex.normal_rgba(relight_preds["feature_normal_raw"], Rt)
+            feat_normal = uvtex.normal_rgba(relight_preds["feature_normal"], Rt)
+        return before, tex_rec, tex_rgb_seg, phys_tex_rgb_seg, feat_normal_raw, feat_normal
+    if phys_tex is not None:
+        phys_tex_rec = (phys_tex * 255.0).clamp_(min=0, max=255)
+    else:
+        phys_tex_rec = torch.zeros_like(tex_mean)
+    gain, bias = _split_gain_bias(relight_preds["tex"])
+    tex_mean.detach().clamp_(min=0, max=255)             # interim["tex_ua"] (:740) clamps the local tex_mean in place
+    tex_rec = tex_mean * gain + bias * self.tex_std
+    if index is not None and hasattr(self, "cal"):
+        tex_rec = self.cal(tex_rec, self.cal.name_to_idx(index["camera"]))
+    before = tex_rec = tex_rec.clamp_(min=0, max=255)
+    if self.impaint_uv:                                  # "still do seam sampler for linear model texture"
+        tex_rec = self.seam_sampler.resample(tex_rec)
+    if rgba:
+        tex_seg = torch.ones_like(tex_rec[:, :1])
+        tex_rgb_seg = torch.cat([tex_rec, tex_seg], dim=1)
+        phys_tex_rgb_seg = torch.cat([phys_tex_rec, tex_seg], dim=1)
+        feat_normal_raw = _normal_colours(relight_preds["feature_normal_raw"], Rt)
+        feat_normal = _normal_colours(relight_preds["feature_normal"], Rt)
+    return before, tex_rec, tex_rgb_seg, phys_tex_rgb_seg, feat_normal_raw, feat_normal
+
+
+def autoencoder_forward(
+    self,
+    pose: torch.Tensor,
+    campos: torch.Tensor,
+    K: torch.Tensor,
+    Rt: torch.Tensor,
+    light_pos: Optional[torch.Tensor] = None,
+    light_intensity: Optional[torch.Tensor] = None,
+    camera_id: Optional[List[str]] = None,
+    frame_id: Optional[torch.Tensor] = None,
+    iteration: Optional[int] = None,
+    **kwargs,
+):
+    """Drop-in for URHand's AutoEncoder.forward (urhand.py:750-990, with forward_tex :711-748): same arguments, same
+    `preds` keys.  Where `self` carries uvtex.TEXTURE_TAIL_FLAG (dropin.patch_urhand(texture_tail=True) sets it on the
+    class) the stretch from relight_preds["tex"] to the four RGBA textures runs on goliath_amd.uvtex: preds["tex_rec"] is
+    then a view of the RGBA texture the renderer takes and CalV5 comes from imgtail.cal_v5_matrix (no host sync per view,
+    the same gradient scales).  Without the flag the reference's own lines run as torch operators, on any device, with
+    the texture size read from the normal map where the reference hard-codes 1024.  The detached `interim` images are
+    built only when vis_feature renders them (nothing else reads them)."""
+    mod = _home(self)
+    fused = bool(getattr(self, uvtex.TEXTURE_TAIL_FLAG, False))
+    index = {"camera": camera_id, "frame": frame_id}
+    bs = pose.shape[0]
+    tex_mean = self.tex_mean.repeat(bs, 1, 1, 1)
+    preds = {}
+    mesh_world = self.lbs_fn.pose(torch.zeros_like(self.lbs_fn.lbs_template_verts), pose)
+    mesh_id_only = self.lbs_fn.lbs_template_verts * self.lbs_fn.global_scaling[0]
+    mesh_id_only = mesh_id_only.repeat(bs, 1, 1)
+    verts_rec = mesh_world
+    hand_pose_aa = mod.matrix_to_axis_angle(
+        mod.euler_angles_to_matrix(torch.flip(pose.reshape(bs, -1, 3), [2]), "ZYX")).reshape(bs, -1)
+    relight_preds = self.decoder_relight(
+        lbs_motion=hand_pose_aa.detach(),
+        id_mesh=mesh_id_only.detach(),
+        tex_mean=tex_mean.detach(),
+        verts_rec=verts_rec.detach(),
+        cam_pos=campos,
+        light_pos=light_pos,
+        light_intensity=light_intensity,
+        seam_sampler=self.seam_sampler,
+        iteration=iteration,
+    )
+    preds.update(interm_features2reg=relight_preds["interm_features2reg"])
+    before, tex_rec, tex_rgb_seg, phys_tex_rgb_seg, feat_normal_raw, feat_normal = texture_stretch(
+        self, relight_preds, tex_mean, index, Rt, fused, rgba=self.rendering_enabled)
+    preds.update(texrec_before_warp=before)
+    old_verts = verts_rec
+    verts_rec = relight_preds["verts_displaced"]
+    preds.update({"geom": verts_rec, "tex_rec": tex_rec})
+    if self.decoder_relight.refine_geo:
+        preds.update(displacement=relight_preds["displacement"])
+    edge_grad = self.training
+    if self.rendering_enabled:
+        feat_render_preds = self.renderer(old_verts, feat_normal_raw, K=K, Rt=Rt)
+        preds.update(old_normals=feat_render_preds["render"][:, :3], uhm_geo_mask=feat_render_preds["render"][:, 3:4],
+                     old_normals_uv=feat_normal_raw)
+        feat_render_preds = self.renderer(verts_rec, feat_normal, K=K, Rt=Rt)
+        preds.update(normals=feat_render_preds["render"][:, :3], normals_uv=feat_normal)
+        render_preds = self.renderer(verts_rec, tex_rgb_seg, K=K, Rt=Rt, edge_grad=edge_grad)
+        rgb_seg = render_preds["render"][:, :4].contiguous()
+        phys_render_preds = self.renderer(verts_rec, phys_tex_rgb_seg, K=K, Rt=Rt, edge_grad=edge_grad)
+        phys_rgb_seg = phys_render_preds["render"][:, :4].contiguous()
+        if self.vis_feature:                             # urhand.py:875-967, forward-only renders of detached maps
+            render3 = lambda verts, tex: self.renderer(verts, tex, K=K, Rt=Rt)["render"][:, :3]
+            shadow = self.decoder_relight.shadow
+            powers = [0, 2, len(self.decoder_relight.spec_powers) - 1]
+            diff_feat = relight_preds["diff_feature"].detach() * 255.0
+            preds.update(
+                diff_feat=render3(verts_rec, diff_feat),
+                spec_feat=torch.stack([render3(verts_rec, relight_preds["spec_feature"][:, p, ...].detach() * 255.0)
+                                       for p in powers], dim=1),
+                shadow_map=render3(verts_rec, relight_preds["shadow"].detach().sum(1) * 255.0) if shadow else None,
+                diff_feat_uv=diff_feat,
+                spec_feat_uv=relight_preds["spec_feature"].detach() * 255.0,
+            )
+            preds.update(                                # raw vertices
+                diff_feat_raw=render3(old_verts, relight_preds["diff_feature_raw"].detach() * 255.0),
+                spec_feat_raw=torch.stack([render3(old_verts, relight_preds["spec_feature_raw"][:, p, ...].detach() * 255.0)
+                                           for p in powers], dim=1),
+                shadow_map_raw=render3(old_verts, relight_preds["shadow_raw"].detach().sum(1) * 255.0) if shadow else None,
+            )
+            for k, v in _interim_images(self, relight_preds, tex_mean).items():
+                if v is not None:
+                    if v.shape[1] == 1:
+                        v_seg = v
+                    elif v.shape[1] == 3:
+                        v_seg = torch.cat([v, torch.ones_like(v[:, :1])], dim=1)
+                    preds[k] = render3(verts_rec, v_seg)
+                    preds[k + "_uv"] = v
+        rgb = rgb_seg[:, :3]
+        seg = rgb_seg[:, 3:4]
+        phys_rgb = phys_rgb_seg[:, :3]
+        if self.blur_enable:
+            blur_padding = int((self.blur_size - 1) // 2)
+            preds.update(rendered_rgb_blur=F.conv2d(rgb, self.blur_kernel, padding=blur_padding, groups=3))
+        preds.update(depth=render_preds["depth_img"], rendered_rgb=rgb, rendered_mask=seg, rendered_phys_rgb=phys_rgb)
+        depth = render_preds["depth_img"].detach()[:, None]
+        preds.update(depth_disc_mask=mod.depth_discontuity_mask(depth))
+    return preds
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -820,6 +820,48 @@ int gol_uvframes_bwd(int B, int V, int F, int S, int T, int Tn, int I, int In, i
                      float* g_posmap, float* g_cam_pos, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * uvtex: URHand's texture tail between the decoder's relight_preds["tex"] and the RGBA textures the renderer takes, one
+ * pass forward and one pass backward (csrc/uvtex.hip).  Replaces, in AutoEncoder.forward_tex / forward,
+ * ca_code/models/urhand.py:721-729 + :741 (gain / bias), :743-745 into CalV5.forward (ca_code/nn/color_cal.py:211-241, as
+ * the per-view cal_M[B,3,3] / cal_b[B,3] of goliath_amd.imgtail.cal_v5_matrix; NULL = no cal), :747 (clamp), :805-807
+ * into resample_tex (ca_code/utils/seams.py:21-25) and :824-825 (alpha packing).
+ *   tex[B,C,S,S], C = 2: (gain, bias) shared by the colours; C = 4: gain 0..2, bias 3; C = 6: gain 0..2, bias 3..5.
+ *   tex_mean[B,3,S,S] (mean_batched != 0) or [1,3,S,S] (0), used clamped to [0, 255]: urhand.py:740 clamps it in place
+ *   (through a detached alias) before :741 reads it -- a no-op for a colour mean; tex_std a scalar (urhand.py:666).
+ *   pre[c] = clamp(sum_j cal_M[c][j] (tex_mean[j] gain[j] + bias[j] tex_std) + cal_b[c], 0, 255)
+ *   out    = (1 - w) pre + w bilinear(pre, uv),  uvs[S,S,2], weights[S,S] (both NULL = no resample: out = pre)
+ * bilinear is grid_sample's (align_corners=False, padding_mode="border"): sample point x = clip(u S - 0.5, 0, S - 1),
+ * likewise y; taps floor and floor + 1; a tap at index S contributes nothing.  The taps' pre values are recomputed, not
+ * read back; texels with w == 0 take no taps and get out = pre exactly.
+ * gol_uvtex_fwd writes texrec_before_warp[B,3,S,S] = pre and tex_rgba[B,4,S,S] = (out, 1).
+ * gol_uvtex_bwd: g_tex_rgba[B,4,S,S] (channel 3 ignored), g_texrec_before_warp[B,3,S,S] (NULL = zero) -> g_tex[B,C,S,S]
+ *   and, with a cal, partials[gol_uvtex_partial_floats(B, S)] = [B, blocks, 16] per-workgroup sums (0..2: cal_b,
+ *   3..11: cal_M row-major, 12..15: zero) that the caller adds over `blocks`.  The seam adjoint is a gather over the
+ *   transposed tap list goliath_amd.uvtex.pack_seams builds (CSR by destination texel t: entries row_start[t] ..
+ *   row_start[t+1] hold src = the band texel whose sample reads t, coeff = w[src] * bilinear weight):
+ *     g_pre[t] = (1 - w[t]) g[t] + sum_e coeff[e] g[src[e]] + g_texrec_before_warp[t]
+ *   then the clamp mask (torch's: passes where 0 <= x <= 255), cal_M^T, and the gain / bias products (a shared gain or
+ *   bias channel gets the sum over the colours).  No gradient to tex_mean (a buffer, detached at urhand.py:778), uvs or
+ *   weights.  No atomics: every output is bitwise reproducible.
+ * gol_pack_rgba_fwd / _bwd: out[B,4,S,S] = (clamp(x scale, lo, hi), 1) for x[B,3,S,S] (urhand.py:788-790 + :826 with
+ *   scale 255); g_x = scale [lo <= x scale <= hi] g_out[:, :3].
+ * gol_normal_rgba (forward only, the reference detaches): urhand.py:828-832 and :843-847, out[B,4,S,S], channel
+ *   c = (1 - sum_j R[c][j] nml[j]) 127.5, channel 3 = 1, R = Rt[:, :3, :3] of Rt[B,3,4] (rt_stride 12) or [B,4,4] (16).
+ * ---------------------------------------------------------------------------------------- */
+int64_t gol_uvtex_partial_floats(int B, int S);
+int gol_uvtex_fwd(int B, int C, int S, int mean_batched, const float* tex, const float* tex_mean, float tex_std,
+                  const float* cal_M, const float* cal_b, const float* uvs, const float* weights,
+                  float* texrec_before_warp, float* tex_rgba, void* stream);
+int gol_uvtex_bwd(int B, int C, int S, int mean_batched, const float* tex, const float* tex_mean, float tex_std,
+                  const float* cal_M, const float* cal_b, const float* weights, const int32_t* row_start,
+                  const int32_t* src, const float* coeff, const float* g_tex_rgba, const float* g_texrec_before_warp,
+                  float* g_tex, float* partials, void* stream);
+int gol_pack_rgba_fwd(int B, int S, float scale, float lo, float hi, const float* x, float* out, void* stream);
+int gol_pack_rgba_bwd(int B, int S, float scale, float lo, float hi, const float* x, const float* g_out, float* g_x,
+                      void* stream);
+int gol_normal_rgba(int B, int S, int rt_stride, const float* nml, const float* Rt, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * uvtopo: the constant UV topology images GeometryModule.__init__ registers (ca_code/utils/geom.py:197-249), without
  * pytorch3d and without the KD-tree (csrc/uvtopo.hip).  Built once per model; forward only, no atomics, reproducible.
  * Texel (r, c) of an [H,W] image is sampled at uv = ((c + 0.5) / W, (r + 0.5) / H); flip_uv != 0 mirrors v (1 - v, in
