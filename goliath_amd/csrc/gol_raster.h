@@ -45,12 +45,30 @@ struct TileCoord { int tile, tx, ty; bool ok; };
 // row (neighbouring tiles share most of their Gaussians -> L2 hits), while the rows of every die are
 // spread over the whole image so the dies stay balanced (contiguous image eighths per die left most of
 // the chip idle: the head covers only the middle rows).  Speed only -- any mapping is correct.
+//
+// The groups of 8 tile rows are not walked from top to bottom either: with the head in the middle rows that order starts
+// and ends every launch with bands of empty tiles, whose workgroups only write constants -- memory traffic with no busy
+// tile resident beside it.  row_order deals the R groups out over the launch from the three thirds of the image in turn
+// (top, middle, bottom, top, ...), so consecutive groups never come from the same third and the empty rows are spread
+// evenly between the busy ones.  The top third is walked upwards from its last group, the other two downwards from their
+// first: the launch begins next to the middle and the group left over when 3 does not divide R is the image's first --
+// walked top to bottom it was the top third's last, and a launch of one view, whose duration is its longest lists' chain,
+// ended on busy tiles with nothing beside them (--views 1: 1.2 % slower than the plain order, profiles/raster_row_order_ab.txt).
+// A bijection on [0, R) for every R: the p with p % 3 == 0, 1, 2 number ceil(R / 3), ceil((R - 1) / 3) and
+// ceil((R - 2) / 3), which are the lengths of the three bands laid end to end.
+__device__ __forceinline__ int row_order(int p, int R) {
+  const int band = p % 3, k = p / 3;
+  const int n0 = (R + 2) / 3, n1 = (R + 1) / 3;
+  return band == 0 ? n0 - 1 - k : k + n0 + (band > 1 ? n1 : 0);
+}
+
 __device__ __forceinline__ TileCoord tile_of_block(int bid, int T, int tiles_x) {
   const int tiles_y = T / tiles_x;
   const int xcd = bid & 7, j = bid >> 3;
   TileCoord tc;
-  const int row_local = j / tiles_x;
-  tc.tx = j - row_local * tiles_x;
+  const int slot_row = j / tiles_x;
+  tc.tx = j - slot_row * tiles_x;   // (the tiles of one row stay consecutive workgroups of one die)
+  const int row_local = row_order(slot_row, (tiles_y + 7) >> 3);
   tc.ty = row_local * 8 + xcd;
   tc.ok = tc.ty < tiles_y;
   tc.tile = tc.ty * tiles_x + tc.tx;
