@@ -677,15 +677,18 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, t
     return urhand_module
 
 
-def patch_hand_teacher(teacher_module=None):
+def patch_hand_teacher(teacher_module=None, olat_fused=False):
     """BASELINE config 5's teacher as a drop-in: `OLATRGBDecoder.forward_rgb` (ca_code/models/hand_teacher_mvp.py:253-494)
     with the per-light deep-shadow march on gol_mvp_shadow_march (goliath_amd.urhand.olat_rgb_decoder_forward_rgb).
+    olat_fused=True binds urhand.olat_rgb_decoder_forward_rgb_fused instead: the UNet input and the OLAT sum on
+    gol_olat_features_fwd / gol_olat_combine_fwd / _bwd as well (goliath_amd.olat); a later call with False restores the default.
     The ordinary ray march of the model already runs on the HIP kernels through `install()` (mvpraymarchlib / utilslib)."""
     from . import urhand
 
     if teacher_module is None:
         import ca_code.models.hand_teacher_mvp as teacher_module
-    teacher_module.OLATRGBDecoder.forward_rgb = urhand.olat_rgb_decoder_forward_rgb
+    teacher_module.OLATRGBDecoder.forward_rgb = (urhand.olat_rgb_decoder_forward_rgb_fused if olat_fused
+                                                 else urhand.olat_rgb_decoder_forward_rgb)
     return teacher_module
 
 

@@ -18,6 +18,11 @@
         * the deep-shadow march (:271-358: L-fold copies of the primitive set and of a 4-channel template, an ordinary
           ray march with with_shadow=True) -> gol_mvp_shadow_march (all lights of a frame share transforms, tree and an
           alpha-only template)
+    olat_rgb_decoder_forward_rgb_fused   the same, with
+        * the UNet input (:371-439: light / view directions in the primitives' frames, mask, UV layout, 1 - shadow)
+                                                          -> gol_olat_features_fwd (goliath_amd.olat), opt-in
+        * the OLAT sum (:468-488: sigmoid, 25 t + 100, relu, intensities, sum over lights, primshadow)
+                                                          -> gol_olat_combine_fwd/bwd, opt-in (dropin.patch_hand_teacher(olat_fused=True))
 
     autoencoder_forward   <- /root/reference/ca_code/models/urhand.py:750-990 (AutoEncoder.forward with forward_tex,
         :711-748); where the model's class carries uvtex.TEXTURE_TAIL_FLAG (dropin.patch_urhand(texture_tail=True)):
@@ -38,7 +43,7 @@ from typing import List, Optional
 import torch
 import torch.nn.functional as F
 
-from . import meshraster, mvp, mvpprims, shadowmap, texdec, uvframes, uvlight, uvtex
+from . import _lib, meshraster, mvp, mvpprims, olat, shadowmap, texdec, uvframes, uvlight, uvtex
 from .imgtail import cal_v5_matrix
 
 
@@ -527,6 +532,65 @@ def olat_rgb_decoder_forward_rgb(
     texolat = 25.0 * tex[:, :, :, 1:] + 100.0
     rgb = (shadowolat * F.relu(texolat) * light_intensity).sum(1).view(B, Z, 3, S, S)
     primshadow = shadow_feat[:, :, None].expand(-1, -1, 3, -1, -1).reshape(B, L, Z, 3, S, S).sum(1) / L
+    output = {"primrgb": rgb, "primshadow": primshadow}
+    if self.training:
+        output["texolat"] = texolat
+    return output
+
+
+def olat_rgb_decoder_forward_rgb_fused(
+    self,
+    campos: torch.Tensor,
+    K: torch.Tensor,
+    Rt: torch.Tensor,
+    primpos: torch.Tensor,
+    primrot: torch.Tensor,
+    primscale: torch.Tensor,
+    primalpha: torch.Tensor,
+    valid_prims: torch.Tensor,
+    joint_feat: torch.Tensor,
+    light_pos: torch.Tensor,
+    light_intensity: torch.Tensor,
+    iteration: Optional[int] = None,
+):
+    """`olat_rgb_decoder_forward_rgb` with the work around the UNet on csrc/olat.hip: same arguments, same output dict.
+    The UNet input comes from one gol_olat_features_fwd (hand_teacher_mvp.py:371-439) and the OLAT sum from
+    gol_olat_combine_fwd / _bwd (:468-488); the deep shadow and the UNet are the unfused function's.  The UNet input does
+    not require grad (goliath_amd.olat.features).  With an input on the CPU, or a light_intensity that requires grad (the
+    combine has no gradient for it), the unfused function runs instead."""
+    tensors = (campos, primpos, primrot, primscale, primalpha, valid_prims, joint_feat, light_pos, light_intensity)
+    if any(not t.is_cuda for t in tensors) or light_intensity.requires_grad:
+        return olat_rgb_decoder_forward_rgb(self, campos, K, Rt, primpos, primrot, primscale, primalpha, valid_prims,
+                                            joint_feat, light_pos, light_intensity, iteration)
+    mod = _home(self)
+    B, L = light_pos.shape[:2]
+    X, Y, Z = self.primsize
+    S = self.uv_size
+    if S != self.n_prim_y * Y or S != self.n_prim_x * X:
+        raise _lib.GoliathHipError(f"uv_size {S} is not {self.n_prim_y} x {self.n_prim_x} primitives of {Y} x {X} texels")
+    f32 = lambda t: t.detach().to(torch.float32).contiguous()
+    with torch.no_grad():
+        shadow = deep_shadow(self, mod, primpos, primrot, primscale, primalpha, valid_prims, light_pos)
+        shadow = f32(shadow).reshape(B * L, self.n_prim_y * self.n_prim_x, Z, Y, X)      # the march's own layout: a view
+        x = olat.features(f32(primpos), f32(primrot), f32(primscale), f32(valid_prims), f32(light_pos), f32(campos), shadow,
+                          self.primsize, self.n_prim_x, self.n_prim_y, self.volradius)
+    joint_feat = joint_feat[:, None].expand(-1, L, -1, -1, -1).reshape(B * L, *joint_feat.shape[-3:])
+    enc_acts = []
+    for i, layer in enumerate(self.enc_layers):          # UNet encoder
+        x = layer(x)
+        enc_acts.append(x)
+        if i < len(self.sizes) - 1:
+            x = F.interpolate(x, scale_factor=0.5, mode="bilinear", recompute_scale_factor=True, align_corners=True)
+    for i, layer in enumerate(self.dec_layers):          # UNet decoder with skip connections
+        if i == 0:
+            x = torch.cat([x, joint_feat], dim=1)
+        else:
+            skip = enc_acts[-i - 1]
+            x = torch.cat([F.interpolate(x, size=skip.shape[2:4], mode="bilinear", align_corners=True), skip], dim=1)
+        x = layer(x)
+    use_shadow = self.training and iteration is not None and iteration < 1000
+    rgb, texolat, primshadow = olat.combine(x.to(torch.float32).contiguous(), light_intensity, shadow, self.primsize,
+                                            self.n_prim_x, self.n_prim_y, use_shadow, self.training)
     output = {"primrgb": rgb, "primshadow": primshadow}
     if self.training:
         output["texolat"] = texolat

@@ -1275,6 +1275,45 @@ int64_t gol_envprefilter_scratch_floats(int B, int He, int We);
 int gol_envprefilter_sg(int B, int H, int W, int He, int We, int S, double sigma, const float* v, const float* env_tex,
                         const float* xi, int64_t seed, int64_t sample_offset, float* scratch, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * olat: the MVP teacher's per-light work around its UNet (csrc/olat.hip), OLATRGBDecoder.forward_rgb of
+ * ca_code/models/hand_teacher_mvp.py.  Primitives are X x Y x Z voxels (primsize), npy x npx of them tile the UV map
+ * [Sy,Sx] = [npy Y, npx X]: texel (h Y + y, w X + x) belongs to primitive k = h npx + w, K = npy npx.
+ * shadow[B L,K,Z,Y,X] is what gol_mvp_shadow_march's caller returns (value / (weight + 1e-5)), in the march's own layout.
+ * gol_olat_features_fwd replaces :371-439, the UNet input x[B L,7 Z,Sy,Sx] (forward only: the reference runs these lines
+ *   under no_grad).  primpos[B,K,3], primrot[B,K,3,3], primscale[B,K,3], valid_prims[K] (float 0 / 1), light_pos[B,L,3],
+ *   campos[B,3]; lin_x[X], lin_y[Y], lin_z[Z] = torch.linspace(-1, 1, .) as device arrays.  Per texel and z:
+ *     local = (lin_z[i % Z], lin_y[(i / Z) % Y], lin_x[i / (Y Z)]) with i = (z Y + y) X + x -- the reference's
+ *       meshgrid([lz, ly, lx]).transpose(1, 3).reshape(3, -1) viewed as [Z,Y,X] (:379-400), AS WRITTEN: for a primitive
+ *       that is not a cube this is not the voxel's own coordinate, and shipped checkpoints were trained with it;
+ *     p = volradius (primpos + R (local / primscale)),  d = (src - p) / max(|src - p|, 1e-12),  out_f = valid sum_e R[e][f] d_e
+ *   channel 3 z + f: src = light_pos[b,l]; channel 3 Z + 3 z + f: src = campos[b], the same for every light of a frame;
+ *   channel 6 Z + z: 1 - shadow[bl,k,z,y,x] (not masked, as there).  A primitive with valid == 0 gets exact zeros in
+ *   channels [0, 6 Z) whatever its transform holds; where src == p the direction is the zero vector.
+ * gol_olat_combine_fwd / _bwd replace :468-488.  tex[B L,4 Z,Sy,Sx] viewed [B,L,Z,4,Sy,Sx]; light_intensity[B,L,3].
+ *     s = use_shadow ? shadow : 1 / (1 + exp(-tex_0)),  texolat_c = 25 tex_{1+c} + 100 (product and sum rounded separately),
+ *     rgb[B,Z,3,Sy,Sx] = sum_l (s relu(texolat_c)) I[b,l,c] in light order,  primshadow[B,Z,3,Sy,Sx] = (sum_l shadow) / L in
+ *     all three channels, dense;  texolat[B,L,Z,3,Sy,Sx] is written when non-NULL (training).
+ *   _bwd: g_rgb[B,Z,3,Sy,Sx] and g_texolat (NULL = absent) -> g_tex, every element written:
+ *     g_tex_0 = s (1 - s) sum_c g_rgb_c relu(texolat_c) I_c, exactly 0 with use_shadow;
+ *     g_tex_{1+c} = 25 (g_texolat_c + [texolat_c > 0] s I_c g_rgb_c): the relu passes nothing at exactly 0, as torch's.
+ *   Everything is recomputed from tex; shadow is read only with use_shadow (NULL allowed otherwise).  No gradient to
+ *   light_intensity or shadow.
+ * A lane owns four consecutive texels of a row (16-byte accesses) when X % 4 == 0 and the maps are 16-byte aligned, one
+ * otherwise; z and the lights are loops inside the lane.  No atomics, no scratch, no host sync: bitwise reproducible,
+ * graph-capturable.  Sy Sx < 2^31, B L < 2^28, B <= 65535 (features), B Z <= 65535 (combine).
+ * ---------------------------------------------------------------------------------------- */
+int gol_olat_features_fwd(int B, int L, int X, int Y, int Z, int npx, int npy, const float* primpos,
+                          const float* primrot, const float* primscale, const float* valid_prims,
+                          const float* light_pos, const float* campos, const float* shadow, float volradius,
+                          const float* lin_x, const float* lin_y, const float* lin_z, float* x, void* stream);
+int gol_olat_combine_fwd(int B, int L, int X, int Y, int Z, int npx, int npy, int use_shadow, const float* tex,
+                         const float* light_intensity, const float* shadow, float* rgb, float* texolat,
+                         float* primshadow, void* stream);
+int gol_olat_combine_bwd(int B, int L, int X, int Y, int Z, int npx, int npy, int use_shadow, const float* tex,
+                         const float* light_intensity, const float* shadow, const float* g_rgb,
+                         const float* g_texolat, float* g_tex, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
