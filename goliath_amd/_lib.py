@@ -43,6 +43,7 @@ _SYMBOLS = [
     "gol_uvtex_partial_floats", "gol_uvtex_fwd", "gol_uvtex_bwd", "gol_pack_rgba_fwd", "gol_pack_rgba_bwd",
     "gol_normal_rgba",
     "gol_olat_features_fwd", "gol_olat_combine_fwd", "gol_olat_combine_bwd",
+    "gol_mvp_tail_fwd", "gol_mvp_tail_bwd_scratch_floats", "gol_mvp_tail_bwd",
 ]
 
 

@@ -692,19 +692,36 @@ def patch_hand_teacher(teacher_module=None, olat_fused=False):
     return teacher_module
 
 
-def patch_hand_mvp(hand_mvp_module=None, full_template=False):
+def patch_hand_mvp(hand_mvp_module=None, full_template=False, fused_tail=False):
     """BASELINE config 5's student as a drop-in: `AutoEncoder.render` (ca_code/models/hand_mvp.py:162-205) assembles the
     compacted primitive template from the decoder slabs with ONE kernel (gol_mvp_template_fwd / _bwd; no full-K copy, no
     per-step nonzero, implicit pixel grid) and `GeomDecoder.forward` (:386-444) forms primpos / primrot / primscale with
     gol_mvp_primtransf_fwd / _bwd (goliath_amd.mvpprims.hand_mvp_render / geom_decoder_forward).  The march itself already
     runs on the HIP kernels.  preds["primrgba"] -- the full-K template only `HandMVPSummary` reads -- is NOT set unless
-    full_template=True (then it is written from the same loads, at the price of one more template-sized store).  Returns
-    the patched module."""
-    from . import mvpprims
+    full_template=True (then it is written from the same loads, at the price of one more template-sized store).
+    fused_tail=True (opt-in; the default leaves everything above as it is): `GeomDecoder.forward` and
+    `RGBSlabDecoder.forward` (:457-474) stop in front of their last ConvTranspose2dWNUB(16 -> TD C) and put a
+    `mvptail.TailHandle` (activation + layer; `.materialize()` gives the slab) into preds["primalpha"] / ["primrgb"]; `render`
+    hands the two to `mvptail.decode_template` (gol_mvp_tail_fwd / _bwd): last layer, bias, 25 x + 100, relu and template in
+    one kernel, no [B,24,1024,1024] / [B,8,1024,1024] slab.  A decoder whose last layer is not the fusable one runs its own
+    lines, and so does full_template=True.  A later call without fused_tail restores the default.  Returns the patched
+    module."""
+    from . import mvpprims, mvptail
 
     if hand_mvp_module is None:
         import ca_code.models.hand_mvp as hand_mvp_module
     setattr(hand_mvp_module.AutoEncoder, mvpprims.FULL_TEMPLATE_FLAG, bool(full_template))
     hand_mvp_module.AutoEncoder.render = mvpprims.hand_mvp_render
     hand_mvp_module.GeomDecoder.forward = mvpprims.geom_decoder_forward
+    rgbdec = getattr(hand_mvp_module, "RGBSlabDecoder", None)
+    if fused_tail:
+        setattr(hand_mvp_module.GeomDecoder, mvptail.FUSED_TAIL_FLAG, True)
+        if "_goliath_own_forward" not in vars(rgbdec):
+            rgbdec._goliath_own_forward = rgbdec.forward
+        rgbdec.forward = mvptail.rgb_decoder_forward
+    else:   # the default touches nothing else; after a fused_tail=True call it puts the decoders back
+        if mvptail.FUSED_TAIL_FLAG in vars(hand_mvp_module.GeomDecoder):
+            setattr(hand_mvp_module.GeomDecoder, mvptail.FUSED_TAIL_FLAG, False)
+        if rgbdec is not None and "_goliath_own_forward" in vars(rgbdec):
+            rgbdec.forward = rgbdec._goliath_own_forward
     return hand_mvp_module

@@ -314,14 +314,23 @@ def hand_mvp_render(self, K, Rt, preds, with_shadow=False):
     """Drop-in for hand_mvp.AutoEncoder.render (hand_mvp.py:162-205): same arguments, same (rayrgb, rayalpha, shadow).
     The template is assembled compacted by ONE kernel from the slabs (no full-K primrgba, no per-step nonzero), the pixel
     grid stays implicit, the primitive transforms are gathered with the cached index.  preds["primrgba"] is set only when
-    the patch was installed with full_template=True (only HandMVPSummary reads it)."""
+    the patch was installed with full_template=True (only HandMVPSummary reads it).  Under patch_hand_mvp(fused_tail=True)
+    preds["primrgb"] / ["primalpha"] are two mvptail.TailHandles and the template comes from mvptail.decode_template (last
+    decoder layers included, no slab); a tensor beside a handle, or full_template=True, materialises the handles."""
     B = K.shape[0]
     valid = preds.get("valid_prims", None)
     full = bool(getattr(self, FULL_TEMPLATE_FLAG, False))
-    res = assemble_template(preds["primrgb"], preds["primalpha"], self.primsize, valid_prims=valid, compact=True, full=full)
-    template = res
-    if full:
-        template, preds["primrgba"] = res
+    from . import mvptail    # (imports this module)
+
+    if not full and mvptail.handles_fit(preds["primrgb"], preds["primalpha"], self.primsize):
+        # patch_hand_mvp(fused_tail=True): both decoders stopped in front of their last layer
+        template = mvptail.decode_handles(preds["primrgb"], preds["primalpha"], self.primsize, valid)
+    else:
+        preds["primrgb"], preds["primalpha"] = mvptail.materialized(preds["primrgb"]), mvptail.materialized(preds["primalpha"])
+        res = assemble_template(preds["primrgb"], preds["primalpha"], self.primsize, valid_prims=valid, compact=True, full=full)
+        template = res
+        if full:
+            template, preds["primrgba"] = res
 
     focal = K[:, :2, :2].contiguous()
     focal = torch.diagonal(focal, dim1=1, dim2=2).contiguous()
@@ -355,7 +364,8 @@ def hand_mvp_render(self, K, Rt, preds, with_shadow=False):
 def geom_decoder_forward(self, pose, joint, iteration=-1):
     """Drop-in for hand_mvp.GeomDecoder.forward (hand_mvp.py:386-444): the same sub-module calls in the same order; the
     tail from the transform deltas to primpos / primrot / primscale (about fifty small launches and as many again backward)
-    is one gol_mvp_primtransf_fwd / _bwd."""
+    is one gol_mvp_primtransf_fwd / _bwd.  Under patch_hand_mvp(fused_tail=True) "primalpha" is a mvptail.TailHandle: the
+    alpha decoder stops in front of its last layer (a decoder that cannot runs its own lines)."""
     mod = _home(self)
     B = pose.shape[0]
 
@@ -377,7 +387,13 @@ def geom_decoder_forward(self, pose, joint, iteration=-1):
     primpos, primrot, primscale = prim_transforms(primposbase, primrotbase, delta_pos, delta_rvec, delta_scale,
                                                   self.prim_scale)
 
-    alpha = self.alphadecoder(joint).view(B, self.primsize_z, 1, self.uv_size, self.uv_size)
-    alpha = F.relu(alpha)
+    alpha = None
+    if getattr(self, "_goliath_fused_tail", False):   # mvptail.FUSED_TAIL_FLAG: a TailHandle in place of the slab
+        from . import mvptail
+
+        alpha = mvptail.tail_handle(self.alphadecoder, joint, self.primsize_z, 1)
+    if alpha is None:
+        alpha = self.alphadecoder(joint).view(B, self.primsize_z, 1, self.uv_size, self.uv_size)
+        alpha = F.relu(alpha)
 
     return {"primalpha": alpha, "primpos": primpos, "primscale": primscale, "primrot": primrot, "geom_lbs": geom_lbs}

@@ -1314,6 +1314,47 @@ int gol_olat_combine_bwd(int B, int L, int X, int Y, int Z, int npx, int npy, in
                          const float* light_intensity, const float* shadow, const float* g_rgb,
                          const float* g_texolat, float* g_tex, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * mvptail: the last layer of the MVP hand model's two decoders written straight into the primitive template
+ * (csrc/mvptail.hip).  Replaces, for both decoders of ca_code/models/hand_mvp.py, the closing
+ * ConvTranspose2dWNUB(16 -> TD C, 4, 2, 1) with its untied bias (:338-340, :384, :455), relu(25 x + 100) (:472) / relu
+ * (:434) and the template assembly of gol_mvp_template_fwd (:172-185, render_raymarcher.py:41-47): the [B,3TD,Sy,Sx] and
+ * [B,TD,Sy,Sx] slabs are never written.  Sy = 2h = ny TH, Sx = 2w = nx TW, K = ny nx.
+ *     x_rgb[B,16,h,w] (NULL: the one-channel template), w_rgb[16,3TD,4,4] (effective weight, ConvTranspose2d layout),
+ *     bias_rgb[3TD,Sy,Sx]; x_alpha[B,16,h,w], w_alpha[16,TD,4,4], bias_alpha[TD,Sy,Sx];
+ *     slot[K], live[K], Kout: as for gol_mvp_template_fwd (slot NULL = identity, then Kout == K; live NULL = all 1)
+ *     pre_rgb[b,3z+c,Y,X] = sum_{ci,ky,kx} x_rgb[b,ci,iy,ix] w_rgb[ci,3z+c,ky,kx] + bias_rgb[3z+c,Y,X],  Y = 2 iy - 1 + ky,
+ *       X = 2 ix - 1 + kx; pre_alpha the same
+ *     out[b, slot[k], z, Y mod TH, X mod TW, c] = relu(rgb_scale pre_rgb + rgb_shift)  (c < 3),  relu(pre_alpha)  (c = 3),
+ *       k = (Y div TH) nx + (X div TW); out[B,Kout,TD,TH,TW,4], 16-byte aligned, or [B,Kout,TD,TH,TW] with x_rgb == NULL
+ *   The conv is exact fp32 (v_mfma_f32_16x16x4_f32), the bias is added to the finished sum, and the affine is rounded as
+ *   PyTorch composes it: the product, then the sum (no FMA; near the kink 25 x cancels against 100), as gol_mvp_template_fwd
+ *   does with act != 0.  A primitive with slot < 0 is not written and tiles that only reach such primitives are not computed;
+ *   live == 0 writes zeros.  Every index 0 .. Kout-1 must occur once in slot, or `out` keeps unwritten primitives.
+ * gol_mvp_tail_bwd: g_out and the saved out, both in template layout; C = 4 or 1 names the layout.
+ *     g_pre = g_out [out > 0], times rgb_scale on the colours, zero for dropped and dead primitives
+ *     g_x_rgb, g_x_alpha [B,16,h,w]; g_w_rgb[16,3TD,4,4], g_w_alpha[16,TD,4,4]; g_bias_rgb[3TD,Sy,Sx], g_bias_alpha[TD,Sy,Sx]:
+ *       each written completely (zeros where nothing arrives), each may be NULL = not wanted
+ *     w_rgb_t[3TD,4,4,16], w_alpha_t[TD,4,4,16]: the weights with the input channel last (needed for g_x_*)
+ *     scratch: gol_mvp_tail_bwd_scratch_floats(B, h, w, TD, C) floats, needed for g_x_* and g_w_*
+ *   Staged: one pass reads g_out / out with 16-byte loads, writes g_pre slab-shaped into scratch and sums it over the
+ *   views, in view order, into the bias gradients; the input gradient is a gather, the weight gradient a split-K GEMM
+ *   whose partial sums a second kernel adds in a fixed order.  No float atomics: two calls are bitwise equal.  g_out == NULL,
+ *   B == 0 or Kout == 0 zero the outputs.
+ * Supported: Ci = 16, 1 <= TD <= 10 (GOL_ERR_UNSUPPORTED otherwise); TH, TW >= 1 with ny TH = 2h, nx TW = 2w;
+ * B, h <= 65535; (2h+2)(2w+2) < 2^25.  All offsets 64-bit.  No allocation, no host sync.
+ * ---------------------------------------------------------------------------------------- */
+int gol_mvp_tail_fwd(int B, int Ci, int h, int w, int TD, int TH, int TW, int ny, int nx, const float* x_rgb,
+                     const float* w_rgb, const float* bias_rgb, const float* x_alpha, const float* w_alpha,
+                     const float* bias_alpha, const int32_t* slot, const int32_t* live, int Kout, float rgb_scale,
+                     float rgb_shift, float* out, void* stream);
+long long gol_mvp_tail_bwd_scratch_floats(int B, int h, int w, int TD, int C);
+int gol_mvp_tail_bwd(int B, int Ci, int h, int w, int TD, int TH, int TW, int ny, int nx, int C, const float* x_rgb,
+                     const float* w_rgb_t, const float* x_alpha, const float* w_alpha_t, const int32_t* slot,
+                     const int32_t* live, int Kout, float rgb_scale, const float* g_out, const float* out,
+                     float* g_x_rgb, float* g_x_alpha, float* g_w_rgb, float* g_w_alpha, float* g_bias_rgb,
+                     float* g_bias_alpha, float* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
