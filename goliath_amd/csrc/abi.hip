@@ -28,3 +28,14 @@ extern "C" int gol_selftest_wave_sum4(const float* in256, float* out128, void* s
   GOL_CHECK_LAUNCH();
   return GOL_OK;
 }
+
+// in512: eight rows of 64 lane values; out64[l] = what gol_wave_sum8 returns in lane l (tests/test_gpu_wave_sum8.py)
+__global__ void selftest_wave_sum8_kernel(const float* __restrict__ in, float* __restrict__ out) {
+  const int l = threadIdx.x;
+  out[l] = gol_wave_sum8(in[l], in[64 + l], in[128 + l], in[192 + l], in[256 + l], in[320 + l], in[384 + l], in[448 + l]);
+}
+extern "C" int gol_selftest_wave_sum8(const float* in512, float* out64, void* stream) {
+  selftest_wave_sum8_kernel<<<1, 64, 0, (hipStream_t)stream>>>(in512, out64);
+  GOL_CHECK_LAUNCH();
+  return GOL_OK;
+}

@@ -102,6 +102,32 @@ __device__ __forceinline__ float gol_wave_sum4(float a, float b, float c, float 
   return gol_row_sum_to_lane15(q);
 }
 
+// Eight wave-wide sums in 17 instructions instead of 2 x 10.  Two 4-way folds leave P (rows: a0 a1 a2 a3) and Q (rows: a4 a5
+// a6 a7) with 16 partials per row; a row then needs no full ladder of its own: P + row_ror:8(P) holds the 8 pair sums of
+// a P row in both halves of the row, the same add on Q overwrites the upper half (bank_mask 0xc: lanes 8-15 of each row)
+// with the pair sums of the Q row, and row_shr 1, 2, 4 (sources left of the row read 0) add the 8 pair sums of each half up.
+// Results: lane 16 r + 7 = sum(a_r), lane 16 r + 15 = sum(a_{4 + r}), r = 0..3:
+//   lane   7  15  23  31  39  47  55  63
+//   sum   a0  a4  a1  a5  a2  a6  a3  a7
+// The masked rotate add is assembly like gol_add_row_shr8 (no builtin adds into part of a row; its s_nop covers the
+// VALU-write -> DPP-read hazard), and so is the last add, which only the result lanes consume (the compiler would sink it
+// into their branch and split it up).  The first rotate add feeds the next one in the same basic block: the DPP combiner
+// fuses it, and the hazard recognizer then places only the wait states the schedule leaves open.
+__device__ __forceinline__ float gol_wave_sum8(float a0, float a1, float a2, float a3, float a4, float a5, float a6,
+                                               float a7) {
+  const float p02 = gol_swap32_sum(a0, a2), p13 = gol_swap32_sum(a1, a3);
+  const float q02 = gol_swap32_sum(a4, a6), q13 = gol_swap32_sum(a5, a7);
+  float p = gol_swap16_sum(p02, p13);        // rows: a0, a1, a2, a3
+  const float q = gol_swap16_sum(q02, q13);  // rows: a4, a5, a6, a7
+  p += gol_dpp_mov0<0x128>(p);  // row_ror:8
+  asm("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xc" : "+v"(p) : "v"(q));
+  p += gol_dpp_mov0<0x111>(p);  // row_shr:1
+  p += gol_dpp_mov0<0x112>(p);  // row_shr:2
+  float r;
+  asm("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(r) : "v"(p));
+  return r;
+}
+
 // element at a 32-bit BYTE offset from a (wave-uniform) base pointer: the SGPR-base + VGPR-offset addressing form
 // (64-bit per-lane address arithmetic costs several quarter-rate vector instructions per access)
 template <typename T>

@@ -488,7 +488,7 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
   bmax = min(bmax, range.y - 1);
   if (bmax < range.x) return;
 
-  float* acc_lane = &s_acc[wave][0][lane >> 4];  // this lane's column (lanes 15, 31, 47, 63 hold sums 0..3 / 4..7)
+  float* acc_lane = &s_acc[wave][0][lane >> 3];  // this lane's column (lane 8 k + 7 holds sum k of the first eight)
   const int n_batches = (bmax - range.x + kBatchB) / kBatchB;
   // A batch is staged through two dependent loads (list id -> the Gaussian's record).  The id of the NEXT batch's entry is
   // fetched while this batch is being worked on, so that only the record gather is left behind the barrier (nothing hides it
@@ -525,12 +525,14 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
       }
     }
     if (bb + 1 < n_batches) { gid_next = entry_id(bb + 1); mask_next = entry_mask(bb + 1); }
-    (&s_touched[0][0])[tid] = 0;  // NW * kBatchB == blockDim
     __syncthreads();
 
     const int t0 = max(0, batch_end - wmax);
     unsigned long long bits = gol_ballot((s_mask[lane] >> wave) & 1);  // kBatchB == 64: one chunk
     if (t0 > 0) bits &= ~0ull << t0;
+    // the entries this wave reduces in this batch, as a wave-uniform 64-bit mask (scalar operations only); stored once,
+    // after the loop -- not as one LDS write per visit into a row that has to be cleared per batch
+    unsigned long long touched = 0ull;
     while (bits) {
       const int t = __builtin_ctzll(bits);
       bits &= bits - 1;
@@ -565,19 +567,23 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
       }
       const float m0 = lane_sum<PPL>(gop), my = lane_sum<PPL>(gy), myy = lane_sum<PPL>(gyy);
       const float mx = m0 * dx, mxx = mx * dx, mxy = my * dx;
-      const float r0 = gol_wave_sum4(g0s, g1s, g2s, m0);
-      const float r1 = gol_wave_sum4(mx, my, mxx, mxy);
-      // the 9th (and 10th) sum: a 6-instruction DPP ladder each (total in lane 63) instead of a third 4-way reduction
+      // the first eight sums in one 8-way reduction: lane 16 r + 7 gets argument r, lane 16 r + 15 argument 4 + r, so with
+      // the even slots first and the odd ones after them lane 8 k + 7 holds slot k
+      const float r0 = gol_wave_sum8(g0s, g2s, mx, mxx, g1s, m0, my, mxy);
+      // the 9th (and 10th) sum: a 6-instruction DPP ladder each (total in lane 63) instead of a second 4-way reduction
       const float r2 = gol_wave_sum_to_lane63(myy);
       const float r3 = EXTRA ? gol_wave_sum_to_lane63(g3) : 0.f;
-      if ((lane & 15) == 15) {
+      if ((lane & 7) == 7) {
         // slot row t of this wave + a 32-bit byte offset (plain pointer arithmetic on the int t becomes a v_mad_u64_u32)
         float* a = gol_at(acc_lane, (unsigned)t * (unsigned)(kAcc * sizeof(float)));
-        a[0] = r0; a[4] = r1;
-        if (lane == 63) { a[8 - 3] = r2; a[9 - 3] = r3; }  // (lane 63's base points at slot 3)
-        s_touched[wave][t] = 1;
+        a[0] = r0;
+        if (lane == 63) { a[8 - 7] = r2; a[9 - 7] = r3; }  // (lane 63's base points at slot 7)
       }
+      touched |= 1ull << t;
     }
+    // lane l owns the flag of entry l (kBatchB == 64): every flag of the row is written, the zeros too, so the row needs no
+    // clearing; the last readers of the previous batch's flags (the merge) are behind the barrier at the top of the batch
+    s_touched[wave][lane] = (int32_t)((touched >> lane) & 1ull);
     __syncthreads();
     if (PACKED) {
       // gradients live in 64-byte records [r g b | opacity | x y | conic a b c | extra | pad]: 16 consecutive

@@ -17,7 +17,8 @@
 //   * a chunk's colours are staged into LDS beside the geometry, per batch (at most 256 x 16 x 4 B = 16 KiB);
 //   * backward: v_alpha is linear in the upstream image gradient, so each chunk adds its own share of v_xy / v_conic /
 //     v_opacity (the v_out_alpha term goes to the chunk of channel 0 only) and writes only its slice of v_colors.  The
-//     CK colour sums and the 6 geometry moments of a visit are reduced over the wave four at a time (gol_wave_sum4),
+//     CK colour sums and the 6 geometry moments of a visit are reduced over the wave four at a time (gol_wave_sum4; eight at a time,
+//     gol_wave_sum8, where they make an even number of fours: chunks of 1, 2, 8 and 16 channels),
 //     parked in per-wave LDS slots, merged across the waves once per batch and leave the workgroup as one float atomic
 //     per Gaussian per tile per component, issued by consecutive lanes (a Gaussian's colour atomics share cache lines).
 #include "gol_raster.h"
@@ -224,7 +225,10 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
   fv T_cur = T_final;
   fv R = bgdot - voa;  // composite of <colour, v_out> over what lies behind (this chunk's channels; see bwd_moments)
 
-  float* acc_lane = &s_acc[wave][0][lane >> 4];  // this lane's column (lanes 15, 31, 47, 63 hold sums 4g + 0 .. 3)
+  // this lane's column: lanes 15, 31, 47, 63 hold sums 4 g + 0 .. 3 of group g; with an even number of groups they are
+  // reduced in pairs (17 instructions per pair instead of 20) and lane 8 k + 7 holds sum 8 p + k of pair p
+  constexpr bool kSum8 = NG % 2 == 0;
+  float* acc_lane = &s_acc[wave][0][kSum8 ? lane >> 3 : lane >> 4];
   const int n_batches = (bmax - range.x + kBatchNdB) / kBatchNdB;
   for (int bb = 0; bb < n_batches; ++bb) {
     __syncthreads();
@@ -281,14 +285,29 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
       s[CK + 0] = m0; s[CK + 1] = mx; s[CK + 2] = my; s[CK + 3] = mx * dx; s[CK + 4] = my * dx; s[CK + 5] = myy;
 #pragma unroll
       for (int k = NS; k < kRow; ++k) s[k] = 0.f;
-      float r[NG];
+      if constexpr (kSum8) {
+        // even slots first, odd ones after them: lane 8 k + 7 then holds slot 8 p + k of pair p (see gol_wave_sum8)
+        float r[NG / 2];
 #pragma unroll
-      for (int gi = 0; gi < NG; ++gi) r[gi] = gol_wave_sum4(s[4 * gi], s[4 * gi + 1], s[4 * gi + 2], s[4 * gi + 3]);
-      if ((lane & 15) == 15) {
-        float* a = gol_at(acc_lane, (unsigned)t * (unsigned)(kRow * sizeof(float)));
+        for (int p = 0; p < NG / 2; ++p)
+          r[p] = gol_wave_sum8(s[8 * p], s[8 * p + 2], s[8 * p + 4], s[8 * p + 6],
+                               s[8 * p + 1], s[8 * p + 3], s[8 * p + 5], s[8 * p + 7]);
+        if ((lane & 7) == 7) {
+          float* a = gol_at(acc_lane, (unsigned)t * (unsigned)(kRow * sizeof(float)));
 #pragma unroll
-        for (int gi = 0; gi < NG; ++gi) a[4 * gi] = r[gi];
-        s_touched[wave][t] = 1;
+          for (int p = 0; p < NG / 2; ++p) a[8 * p] = r[p];
+          s_touched[wave][t] = 1;
+        }
+      } else {
+        float r[NG];
+#pragma unroll
+        for (int gi = 0; gi < NG; ++gi) r[gi] = gol_wave_sum4(s[4 * gi], s[4 * gi + 1], s[4 * gi + 2], s[4 * gi + 3]);
+        if ((lane & 15) == 15) {
+          float* a = gol_at(acc_lane, (unsigned)t * (unsigned)(kRow * sizeof(float)));
+#pragma unroll
+          for (int gi = 0; gi < NG; ++gi) a[4 * gi] = r[gi];
+          s_touched[wave][t] = 1;
+        }
       }
     }
     __syncthreads();

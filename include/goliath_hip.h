@@ -41,6 +41,9 @@ const char* gol_last_error(void);
  * out128[0..63] = per-lane result of the 4-way swap reduction (lanes 15/31/47/63 = sums of
  * a/b/c/d), out128[64..127] = per-lane result of the DPP ladder (lane 63 = sum of a). */
 int gol_selftest_wave_sum4(const float* in256, float* out128, void* stream);
+/* The 8-way reduction: in512 = 8 x 64 floats (a0 .. a7 per lane); out64 = its per-lane result.  Lane 16 r + 7 holds
+ * sum(a_r) and lane 16 r + 15 sum(a_{4+r}), r = 0..3; the other lanes hold partial sums. */
+int gol_selftest_wave_sum8(const float* in512, float* out64, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * sgutils -- spherical-Gaussian specular lobe evaluation.
