@@ -6,44 +6,26 @@
 //     xin[b,ci,r,c] = in_scale x[b,ci,r,c] + in_shift inside the image, 0 outside (the pad comes after the affine)
 //     y[b,co,Y,X]   = lrelu( sum_{ci,ky,kx} xin[b,ci,2Y-1+ky,2X-1+kx] W[co,ci,ky,kx] + bias[co,Y,X] )
 // run there as a MIOpen convolution, an ATen add and an ATen leaky_relu (and five kernels backward).  The convolution is the
-// exact adjoint of trunk.hip's transposed one, so the three GEMM formulations are trunk.hip's with the roles exchanged:
-//   fwd     the form of trunk_bwd_x_kernel -- a gather, no atomics: D[co][pixel] += A[co][ky] B[ky][pixel] per (ci, kx) on
-//           v_mfma_f32_16x16x4_f32 (exact fp32), K = the 4 rows of the window, so a lane's four kx come from one 16-byte
-//           load.  Weights go through an LDS tile per K stage of 4 input channels (Ci = 1..4: the stage's missing
-//           channels are ZERO WEIGHTS, and no channel of x that does not exist is read); the affine is applied to the
-//           loaded values, bias + LeakyReLU to the accumulators; nothing but y is written.
+// exact adjoint of trunk.hip's transposed one (tests/test_gpu_conv4s2_adjoint.py), so the three formulations of
+// gol_conv4s2.h are taken with the roles exchanged (fine grid = x, coarse grid = y):
+//   fwd     row gather, reduction over ci in K stages of 4 (Ci = 1..4: the stage's missing channels are ZERO WEIGHTS, and
+//           no channel of x that does not exist is read); the affine is applied to the loaded values, bias + LeakyReLU
+//           to the accumulators; nothing but y is written.
 //   bwd     g_pre = g_y (y > 0 ? 1 : leak) is formed while loading (leak > 0 keeps the sign, so y carries the mask):
-//     bwd_x   the form of trunk_fwd_kernel: the 2x2 quad {2m-1, 2m} x {2k-1, 2k} of x reads the 2x2 block {m-1, m} x
-//             {k-1, k} of g_pre and uses each of the 16 taps once; the four parity classes share the B operand.  W is
-//             taken in the forward's layout [Co,Ci,4,4] (reduction channel first: no permuted copy is needed);
-//     bwd_w   the form of trunk_bwd_w_kernel with x and g in each other's role: per (16 co x 16 ci) tile pair a GEMM over
-//             pixels, 16 accumulator tiles (one per tap); g_pre[16 NCO][64] and the matching xin window [16 ci][4 rows]
-//             [130 cols] are staged in LDS, up to four co tiles sharing a staged window (Ci = 1..4: B columns = (ci, dx),
-//             a quarter of the MFMAs, see enc_bwd_w_kernel); K is split over workgroups,
-//             partial sums go to scratch, a second kernel adds them in a fixed order (no float atomics: bitwise
-//             reproducible);
+//     bwd_x   quad form, reduction over co in K stages of 8.  W is taken in the forward's layout [Co,Ci,4,4] (reduction
+//             channel first: no permuted copy is needed);
+//     bwd_w   weight gradient with x and g in each other's role: per (16 co x 16 ci) tile pair, g_pre[16 NCO][64] is the
+//             coarse side and xin [16 ci] the window, up to four co tiles sharing a staged window (Ci = 1..4: B columns =
+//             (ci, dx), a quarter of the MFMAs, see enc_bwd_w_kernel);
 //     bwd_b   g_bias[co,Y,X] = sum_b g_pre, one streaming pass.
-// gol_uniform is a copy of trunk.hip's (sharing it is a follow-up behind the resource-usage gate).
-#include "gol_common.h"
+#include "gol_conv4s2.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 struct EncDims {
   int B, Ci, Co, H, W;  // x [B,Ci,H,W] -> y [B,Co,H/2,W/2]
   float leak, in_scale, in_shift;
 };
-
-// a wave-uniform pointer pinned to SGPRs: loads through gol_at(gol_uniform(base), lane_offset) take the scalar-base +
-// 32-bit lane-offset form
-template <typename T>
-__device__ __forceinline__ T* gol_uniform(T* q) {
-  const uint64_t v = reinterpret_cast<uint64_t>(q);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return reinterpret_cast<T*>(((uint64_t)hi << 32) | lo);
-}
 
 constexpr int kFwdKC = 4;  // input channels per K stage of the forward (Ci is a multiple of 8, or 1..4 zero-padded to 4)
 constexpr int kBxKC = 8;   // output channels per K stage of the input gradient (Co is a multiple of 16)
@@ -57,6 +39,8 @@ constexpr int kBxKC = 8;   // output channels per K stage of the input gradient 
 // leaves the row) and the values shift by one (WIDE; rows of fewer than 4 floats, W = 2, take clamped scalar loads).
 // MFMA operands: A[i = lane & 15][k = lane >> 4], B[k][j = lane & 15], D[i = 4 (lane >> 4) + r][j].
 // s_w[ci][kx][ct][channel i][ky]: the A operand of (ci, kx, ct) is 64 consecutive floats (element 4 i + k).
+// (written out, not a gol_conv4s2.h helper: as row_gemm + callbacks, shared with trunk_bwd_x_kernel, the VGPR counts of
+// three instances moved or the loaded block spilled: profiles/LOG.md "conv4s2")
 template <int CT, bool WIDE>
 __global__ __launch_bounds__(256) void enc_fwd_kernel(const EncDims p, const float* __restrict__ px,
                                                       const float* __restrict__ pw, const float* __restrict__ pbias,
@@ -164,6 +148,8 @@ __global__ __launch_bounds__(256) void enc_fwd_kernel(const EncDims p, const flo
 // uses each of the 16 taps once, so every parity class (a,q) is a GEMM D[ci][quad] = A[ci][(co,tap)] B[(co,tap)][quad],
 // K = the 4 taps of one co, and B is shared by the four classes.  grid (B, tiles of 64 quads, groups of 16 CT input
 // channels); one wave = 16 quads (linear over the (H/2+1) x (W/2+1) quad grid) x 16 CT channels x 4 classes.
+// (written out, not a gol_conv4s2.h helper: as quad_gemm + callbacks, shared with trunk_fwd_kernel, the epilogue's
+// address arithmetic grew by 20-68 instructions per instance: profiles/LOG.md "conv4s2")
 template <int CT>
 __global__ __launch_bounds__(256) void enc_bwd_x_kernel(const EncDims p, const float* __restrict__ pw,
                                                         const float* __restrict__ py, const float* __restrict__ pg,
@@ -263,11 +249,8 @@ __global__ __launch_bounds__(256) void enc_bwd_x_kernel(const EncDims p, const f
 // SMALL (Ci = 1..4, the first layer): a 16-wide ci tile would carry 12 or more zero columns through every MFMA, so the B
 // operand's 16 columns are (ci 0..3) x (dx 0..3) instead -- one MFMA per (row dy, pixel) covers the four dx, a quarter of
 // the instructions -- and the window holds 4 planes, one per wave.
-constexpr int kWTile = 64;
-constexpr int kXRow = 2 * kWTile + 4;   // 130 used
-constexpr int kXPlane = 4 * kXRow + 2;  // == 18 (mod 32): the 8-byte reads of a lane group's 16 planes cover the 32 banks
-constexpr int kGRow = kWTile + 4;
-
+// (the loaders, the MFMA nest and the wave sum are written out: as gol_conv4s2.h helpers they changed the VGPR counts of the
+// weight-gradient kernels, profiles/LOG.md "conv4s2")
 template <int NCO, bool SMALL>
 __global__ __launch_bounds__(256) void enc_bwd_w_kernel(const EncDims p, const float* __restrict__ px,
                                                         const float* __restrict__ py, const float* __restrict__ pg,
@@ -275,10 +258,10 @@ __global__ __launch_bounds__(256) void enc_bwd_w_kernel(const EncDims p, const f
   constexpr int NP = 4 / NCO;  // waves that share a channel tile split the tile's 64 pixels
   constexpr int XPL = SMALL ? 4 : 16;   // window planes
   constexpr int NSEG = XPL;             // (plane, row) segments of the window per wave
-  constexpr int kMem = XPL * kXPlane + NCO * 16 * kGRow;
+  constexpr int kMem = XPL * kWinPlane + NCO * 16 * kPixRow;
   __shared__ __attribute__((aligned(16))) float s_mem[kMem > 16 * 256 ? kMem : 16 * 256];  // (the reduction image below)
   float* s_x = s_mem;
-  float* s_g = s_mem + XPL * kXPlane;
+  float* s_g = s_mem + XPL * kWinPlane;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, kq = lane >> 4;
   const int col = wave % NCO, part = wave / NCO;
   const int H = p.H, W = p.W, h = H >> 1, w = W >> 1, Ci = p.Ci, Co = p.Co;
@@ -332,7 +315,7 @@ __global__ __launch_bounds__(256) void enc_bwd_w_kernel(const EncDims p, const f
     // (channels past Co hold a copy of a valid row: they only reach accumulator rows that the reduce kernel drops)
     const bool gv = ix0 + lane < w;
 #pragma unroll
-    for (int u = 0; u < 4 * NCO; ++u) s_g[(wave + 4 * u) * kGRow + lane] = gv ? rg[u] * (ry[u] > 0.f ? 1.f : leak) : 0.f;
+    for (int u = 0; u < 4 * NCO; ++u) s_g[(wave + 4 * u) * kPixRow + lane] = gv ? rg[u] * (ry[u] > 0.f ? 1.f : leak) : 0.f;
 #pragma unroll
     for (int sgm = 0; sgm < NSEG; ++sgm) {
       const int seg = wave * NSEG + sgm, pl = seg >> 2, dy = seg & 3, oy = 2 * iy - 1 + dy;
@@ -340,12 +323,12 @@ __global__ __launch_bounds__(256) void enc_bwd_w_kernel(const EncDims p, const f
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int cl = lane + 64 * u, cc = 2 * ix0 - 1 + cl;
-        s_x[pl * kXPlane + dy * kXRow + cl] = (rv && cc >= 0 && cc < W) ? fmaf(in_scale, rx[2 * sgm + u], in_shift) : 0.f;
+        s_x[pl * kWinPlane + dy * kWinRow + cl] = (rv && cc >= 0 && cc < W) ? fmaf(in_scale, rx[2 * sgm + u], in_shift) : 0.f;
       }
     }
     if (tid < 8 * NSEG) {
       const int pl = lseg >> 2, dy = lseg & 3, oy = 2 * iy - 1 + dy, cc = 2 * ix0 - 1 + lcl;
-      s_x[pl * kXPlane + dy * kXRow + lcl] =
+      s_x[pl * kWinPlane + dy * kWinRow + lcl] =
           (oy >= 0 && oy < H && ci0 + pl < Ci && cc < W) ? fmaf(in_scale, rlx, in_shift) : 0.f;
     }
   };
@@ -363,20 +346,20 @@ __global__ __launch_bounds__(256) void enc_bwd_w_kernel(const EncDims p, const f
 #pragma unroll
     for (int c = 0; c < NCO; ++c) {
       const int xl = (part * NCO + c) * 16 + 4 * kq;  // this lane's 4 output pixels (K slice) inside the tile
-      const float4 ga4 = *reinterpret_cast<const float4*>(&s_g[(col * 16 + l15) * kGRow + xl]);
+      const float4 ga4 = *reinterpret_cast<const float4*>(&s_g[(col * 16 + l15) * kPixRow + xl]);
       const float ga[4] = {ga4.x, ga4.y, ga4.z, ga4.w};
       if constexpr (SMALL) {  // B column l15 = (ci l15 >> 2, dx l15 & 3): acc[dy][0] is D[co][(ci, dx)]
-        const float* xp = &s_x[(l15 >> 2) * kXPlane + 2 * xl + (l15 & 3)];
+        const float* xp = &s_x[(l15 >> 2) * kWinPlane + 2 * xl + (l15 & 3)];
 #pragma unroll
         for (int dy = 0; dy < 4; ++dy)
 #pragma unroll
           for (int t = 0; t < 4; ++t)
-            acc[dy][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[t], xp[dy * kXRow + 2 * t], acc[dy][0], 0, 0, 0);
+            acc[dy][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[t], xp[dy * kWinRow + 2 * t], acc[dy][0], 0, 0, 0);
         continue;
       }
 #pragma unroll
       for (int dy = 0; dy < 4; ++dy) {
-        const float* xp = &s_x[l15 * kXPlane + dy * kXRow + 2 * xl];  // column 0 of s_x is global column 2 ix0 - 1
+        const float* xp = &s_x[l15 * kWinPlane + dy * kWinRow + 2 * xl];  // column 0 of s_x is global column 2 ix0 - 1
         float xv[10];
 #pragma unroll
         for (int q = 0; q < 10; q += 2) {
@@ -427,51 +410,24 @@ __global__ __launch_bounds__(256) void enc_bwd_w_kernel(const EncDims p, const f
   }
 }
 
-// gw[co,ci,tap] = sum over the K blocks (written once).  grid (16 taps x 16 co rows, channel tiles): a workgroup owns 16
-// outputs and sums them as 16 interleaved K slices that meet in LDS in slice order -- a fixed order.
+// gw[co,ci,tap] = sum over the K blocks (written once).  grid (16 taps x 16 co rows, channel tiles)
 __global__ __launch_bounds__(256) void enc_bwd_w_reduce_kernel(const EncDims p, int NCO, int nblk,
                                                                const float* __restrict__ scratch,
                                                                float* __restrict__ gw) {
-  __shared__ float s_part[16][16];
-  const int tap = blockIdx.x >> 4, row = blockIdx.x & 15, cl = threadIdx.x & 15, ks = threadIdx.x >> 4;
+  const int tap = blockIdx.x >> 4, row = blockIdx.x & 15, cl = threadIdx.x & 15;
   const int nci = (p.Ci + 15) >> 4, grp = blockIdx.y / NCO, c = blockIdx.y - grp * NCO;
   const int cog = grp / nci, cit = grp - cog * nci;
   const int co = (cog * NCO + c) * 16 + row, ci = cit * 16 + cl;
   if (co >= p.Co) return;  // block-uniform: a tile past the end of the last group
-  const float* src = scratch + (((size_t)blockIdx.y * nblk) * 16 + tap) * 256 + row * 16 + cl;
-  float acc = 0.f;
-#pragma unroll 4
-  for (int k = ks; k < nblk; k += 16) acc += src[(size_t)k * 16 * 256];
-  s_part[ks][cl] = acc;
-  __syncthreads();
-  if (ks == 0 && ci < p.Ci) {  // (columns past Ci: Ci = 1..4 or a ragged last tile)
-#pragma unroll
-    for (int q = 1; q < 16; ++q) acc += s_part[q][cl];
-    gw[((size_t)co * p.Ci + ci) * 16 + tap] = acc;
-  }
+  wgrad_reduce16(scratch + (((size_t)blockIdx.y * nblk) * 16 + tap) * 256 + row * 16 + cl, nblk,
+                 gw + ((size_t)co * p.Ci + ci) * 16 + tap, ci < p.Ci);  // (columns past Ci: Ci = 1..4 or a ragged last tile)
 }
 
-// ---- bias gradient ---------------------------------------------------------------------------------------------------
-// gbias[n] = sum_b gpre[b,n] over the Co * H/2 * W/2 plane elements, four per thread
+// ---- bias gradient: over the Co * H/2 * W/2 plane elements, four per thread --------------------------------------------
 __global__ __launch_bounds__(256) void enc_bwd_b_kernel(const EncDims p, const float* __restrict__ py,
                                                         const float* __restrict__ pg, float* __restrict__ pgb) {
-  const size_t N4 = (size_t)(p.Co >> 2) * (p.H >> 1) * (p.W >> 1);  // float4 count of one view
-  const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= N4) return;
-  const float leak = p.leak;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int b = 0; b < p.B; ++b) {
-    const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pg) + (size_t)b * N4 + n);
-    const f32x4 yv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(py) + (size_t)b * N4 + n);
-    s.x += gv.x * (yv.x > 0.f ? 1.f : leak);
-    s.y += gv.y * (yv.y > 0.f ? 1.f : leak);
-    s.z += gv.z * (yv.z > 0.f ? 1.f : leak);
-    s.w += gv.w * (yv.w > 0.f ? 1.f : leak);
-  }
-  reinterpret_cast<float4*>(pgb)[n] = s;
+  lrelu_bias_grad((size_t)(p.Co >> 2) * (p.H >> 1) * (p.W >> 1), p.B, p.leak, py, pg, pgb);
 }
-
-bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 int check_common(int B, int Ci, int Co, int H, int W, float leak) {
   GOL_REQUIRE(B >= 0 && Ci > 0 && Co > 0 && H > 0 && W > 0, "bad sizes");
@@ -494,13 +450,9 @@ int check_common(int B, int Ci, int Co, int H, int W, float leak) {
 int bwd_w_nco(int Co) { return Co > 32 ? 4 : (Co > 16 ? 2 : 1); }
 int bwd_w_groups(int Ci, int Co) { return gol_cdiv(Co, 16 * bwd_w_nco(Co)) * gol_cdiv(Ci, 16); }
 
+// one round of the resident workgroups: 2 per CU (registers), 4 of the small-Ci variant
 int bwd_w_blocks(int B, int Ci, int Co, int H, int W) {
-  const long long ntiles = (long long)B * (H / 2) * gol_cdiv(W / 2, kWTile), pairs = bwd_w_groups(Ci, Co);
-  // one round of the resident workgroups: 2 per CU (registers), 4 of the small-Ci variant
-  const long long target = Ci <= 4 ? 1024 : 512;
-  long long nblk = (target + pairs - 1) / pairs;
-  nblk = nblk > ntiles ? ntiles : nblk;
-  return (int)(nblk < 1 ? 1 : nblk);
+  return wgrad_blocks((long long)B * (H / 2) * gol_cdiv(W / 2, kWTile), bwd_w_groups(Ci, Co), Ci <= 4 ? 1024 : 512);
 }
 
 }  // namespace
@@ -511,7 +463,7 @@ extern "C" int gol_enc_conv_fwd(int B, int Ci, int Co, int H, int W, float leak,
   if (rc != GOL_OK) return rc;
   if (B == 0) return GOL_OK;
   GOL_REQUIRE(x && w_eff && bias && y, "null pointer");
-  GOL_REQUIRE(aligned16(w_eff), "w_eff must be 16-byte aligned");
+  GOL_REQUIRE(gol_aligned16(w_eff), "w_eff must be 16-byte aligned");
   const EncDims p{B, Ci, Co, H, W, leak, in_scale, in_shift};
   hipStream_t s = (hipStream_t)stream;
   const int tiles = gol_cdiv((long long)(H / 2) * (W / 2), 64);
@@ -546,9 +498,9 @@ extern "C" int gol_enc_conv_bwd(int B, int Ci, int Co, int H, int W, float leak,
     return GOL_OK;
   }
   GOL_REQUIRE(y && g_y, "null pointer");
-  GOL_REQUIRE(!g_x || (w_eff && aligned16(w_eff)), "g_x needs w_eff (16-byte aligned)");
+  GOL_REQUIRE(!g_x || (w_eff && gol_aligned16(w_eff)), "g_x needs w_eff (16-byte aligned)");
   GOL_REQUIRE(!g_w || (x && scratch), "g_w needs x and scratch");
-  GOL_REQUIRE(!g_bias || (aligned16(y) && aligned16(g_y) && aligned16(g_bias)), "g_bias needs 16-byte aligned y, g_y, g_bias");
+  GOL_REQUIRE(!g_bias || (gol_aligned16(y) && gol_aligned16(g_y) && gol_aligned16(g_bias)), "g_bias needs 16-byte aligned y, g_y, g_bias");
   const EncDims p{B, Ci, Co, H, W, leak, in_scale, in_shift};
   if (g_x) {
     const int tiles = gol_cdiv((long long)(H / 2 + 1) * (W / 2 + 1), 64);

@@ -180,7 +180,6 @@ __global__ __launch_bounds__(THREADS) void finalize_kernel(const double* __restr
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -209,7 +208,7 @@ extern "C" int gol_envspin_frame(int B, int H, int W, const float* image, const 
   float* rotated = scratch;
   double* probe = reinterpret_cast<double*>(scratch + (size_t)B * 3 * HW);   // B 3 H W is even (W is): 8-byte aligned
   const dim3 grid(gol_cdiv(HW, PIX * THREADS), B);
-  if (HW % PIX == 0 && aligned16(rotated) && (!envbg || aligned16(envbg)))
+  if (HW % PIX == 0 && gol_aligned16(rotated) && (!envbg || gol_aligned16(envbg)))
     rotate_kernel<true><<<grid, THREADS, 0, st>>>(H, W, image, rot, perc90, rotated, envbg);
   else
     rotate_kernel<false><<<grid, THREADS, 0, st>>>(H, W, image, rot, perc90, rotated, envbg);

@@ -40,6 +40,7 @@ void gol_set_error(const char* fmt, ...);
   } while (0)
 
 static inline int gol_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+static inline bool gol_aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // ---- wave64 reductions through DPP (no LDS traffic) ---------------------------------------
 // Sum over the 64 lanes; the total is valid in lane 63 (row_shr 1,2,3 + row_bcast 15/31,
@@ -133,6 +134,15 @@ __device__ __forceinline__ float gol_wave_sum8(float a0, float a1, float a2, flo
 template <typename T>
 __device__ __forceinline__ T* gol_at(T* base, unsigned byte_off) {
   return reinterpret_cast<T*>(reinterpret_cast<char*>(const_cast<typename std::remove_const<T>::type*>(base)) + byte_off);
+}
+
+// a wave-uniform pointer pinned to SGPRs: loads through gol_at(gol_uniform(base), lane_offset) take the scalar-base +
+// 32-bit lane-offset form (otherwise the loop-invariant lane part is folded into a 64-bit per-lane base: 2 VGPRs per load)
+template <typename T>
+__device__ __forceinline__ T* gol_uniform(T* q) {
+  const uint64_t v = reinterpret_cast<uint64_t>(q);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return reinterpret_cast<T*>(((uint64_t)hi << 32) | lo);
 }
 
 // lane mask of a predicate as a scalar (s_and with exec); HIP's __ballot(int) goes through an int (v_cndmask + v_cmp_ne)

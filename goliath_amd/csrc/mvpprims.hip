@@ -390,7 +390,6 @@ __global__ __launch_bounds__(THREADS) void primtransf_bwd_kernel(int M, const fl
   for (int j = 0; j < 3; ++j) g_delta_rvec[(size_t)i * 3 + j] = g_n[j] * inv + g_theta * n[j];
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -407,7 +406,7 @@ extern "C" int gol_mvp_template_fwd(int B, int TD, int TH, int TW, int ny, int n
   TPL_REQUIRE_SIZES();
   if (B == 0 || (!out_full && Kout == 0)) return GOL_OK;
   GOL_REQUIRE(alpha && (out || Kout == 0), "null pointer");
-  GOL_REQUIRE(aligned16(out) && aligned16(out_full), "the templates must be 16-byte aligned");
+  GOL_REQUIRE(gol_aligned16(out) && gol_aligned16(out_full), "the templates must be 16-byte aligned");
   const TplGeom g{TD, TH, TW, ny, nx, out ? Kout : 0, act != 0, rgb_scale, rgb_shift};
   const long long plane = (long long)ny * TH * nx * TW;
   hipStream_t st = (hipStream_t)stream;
@@ -430,7 +429,7 @@ extern "C" int gol_mvp_template_bwd(int B, int TD, int TH, int TW, int ny, int n
   if (B == 0) return GOL_OK;
   GOL_REQUIRE(g_alpha, "null pointer");
   GOL_REQUIRE(!act || (alpha && (rgb || !g_rgb)), "the activation's mask needs the forward's input");
-  GOL_REQUIRE(aligned16(g_out) && aligned16(g_out_full), "the template gradients must be 16-byte aligned");
+  GOL_REQUIRE(gol_aligned16(g_out) && gol_aligned16(g_out_full), "the template gradients must be 16-byte aligned");
   const TplGeom g{TD, TH, TW, ny, nx, g_out ? Kout : 0, act != 0, rgb_scale, rgb_shift};
   const long long plane = (long long)ny * TH * nx * TW;
   hipStream_t st = (hipStream_t)stream;

@@ -16,28 +16,19 @@
 //   bwd     staged: one pass reads g_out and out in template layout (16-byte loads: three colours and the alpha of a depth
 //           slice), forms g_pre = g_out [out > 0] (colours times rgb_scale, zero for dropped and dead primitives), writes
 //           it slab-shaped into scratch and sums it over the views into the bias gradients.  The input gradient is the
-//           gather form of tail.hip, the weight gradient the split-K GEMM of trunk.hip with a fixed-order reduction.  No
-//           float atomics.
-#include "gol_common.h"
+//           16-channel scalar gather and the weight gradient the split-K GEMM with the fixed-order reduction of
+//           gol_conv4s2.h (one tile of 16 input channels, g_pre read as it is, plain run order).  No float atomics.
+#include "gol_conv4s2.h"
 
 namespace {
 
 constexpr int kCi = 16;     // input channels of both last layers (hand_mvp.py:338)
 constexpr int kMaxTD = 10;  // 3 TD <= 32: two row tiles of colour
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct MvpTailDims {
   int B, h, w, TD, TH, TW, ny, nx, Kout;
   float scale, shift;
 };
-
-// a wave-uniform pointer pinned to SGPRs (cf. trunk.hip)
-template <typename T>
-__device__ __forceinline__ T* mt_uniform(T* q) {
-  const uint64_t v = reinterpret_cast<uint64_t>(q);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return reinterpret_cast<T*>(((uint64_t)hi << 32) | lo);
-}
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
 // grid (B, K blocks): the B views of a run of tiles are neighbours in dispatch order, so a bias tile comes from memory
@@ -288,38 +279,10 @@ __global__ __launch_bounds__(256) void mvptail_gpre_kernel(const MvpTailDims p, 
   if (pgba) pgba[(size_t)z * HWo + pix] = s[3];
 }
 
-// ---- input gradient (tail_conv_bwd_x_kernel's gather form; wt = W as [CH,4,4,16]) --------------------------------------
-// gx[b,ci,iy,ix] = sum_{ch,dy,dx} g[b,ch,2iy-1+dy,2ix-1+dx] W[ci,ch,dy,dx]: one lane = one input pixel x 16 channels
+// ---- input gradient: the scalar gather of gol_conv4s2.h; wt = W as [CH,4,4,16] --------------------------------------------
 __global__ __launch_bounds__(256) void mvptail_bwd_x_kernel(int h, int w, int CH, const float* __restrict__ pwt,
                                                             const float* __restrict__ pg, float* __restrict__ pgx) {
-  const int ix = blockIdx.x * 256 + threadIdx.x, iy = blockIdx.y, b = blockIdx.z;
-  if (ix >= w) return;
-  const size_t HWi = (size_t)h * w, HWo = 4 * HWi;
-  const float* gb = pg + (size_t)b * CH * HWo;
-  float acc[kCi];
-#pragma unroll
-  for (int ci = 0; ci < kCi; ++ci) acc[ci] = 0.f;
-#pragma unroll
-  for (int dy = 0; dy < 4; ++dy) {
-    const int oy = 2 * iy - 1 + dy;
-    if (oy < 0 || oy >= 2 * h) continue;  // block-uniform
-    const int ox0 = 2 * ix - 1;
-    const bool ok0 = ox0 >= 0, ok3 = ox0 + 3 < 2 * w;
-    for (int ch = 0; ch < CH; ++ch) {
-      const float* gr = gb + (size_t)ch * HWo + (size_t)oy * (2 * w) + ox0;
-      float gv[4];  // unconditional loads (edge lanes re-read a neighbour), then masked
-      gv[0] = gr[ok0 ? 0 : 1]; gv[1] = gr[1]; gv[2] = gr[2]; gv[3] = gr[ok3 ? 3 : 2];
-      gv[0] = ok0 ? gv[0] : 0.f; gv[3] = ok3 ? gv[3] : 0.f;
-#pragma unroll
-      for (int dx = 0; dx < 4; ++dx) {
-        const float* wq = pwt + ((size_t)(ch * 4 + dy) * 4 + dx) * 16;  // wave-uniform
-#pragma unroll
-        for (int ci = 0; ci < kCi; ++ci) acc[ci] += gv[dx] * wq[ci];
-      }
-    }
-  }
-#pragma unroll
-  for (int ci = 0; ci < kCi; ++ci) pgx[((size_t)b * kCi + ci) * HWi + (size_t)iy * w + ix] = acc[ci];
+  gather_bwd_x16(h, w, CH, pwt, pg, pgx);
 }
 
 // ---- weight gradient (trunk_bwd_w_kernel with one tile of 16 input channels, g_pre read as it is) ------------------------
@@ -327,16 +290,13 @@ __global__ __launch_bounds__(256) void mvptail_bwd_x_kernel(int h, int w, int CH
 // workgroup walks tiles of one view x one input row x 64 input pixels: x[16][64] and the matching window
 // [16 ch][4 rows][130 cols] are staged in LDS, each wave feeds its 16-pixel chunk to 64 MFMAs (16 taps x 4 pixels per
 // instruction); the waves' sums meet in LDS in wave order and leave as one partial [16 taps][16 ci][16 ch].
-constexpr int kWTile = 64;
-constexpr int kGRow = 2 * kWTile + 4;   // 130 used
-constexpr int kGPlane = 4 * kGRow + 2;  // == 2 (mod 32): the 16 planes of a lane group spread over the banks
-constexpr int kXRow = kWTile + 4;
-
+// (the loaders, the MFMA nest and the wave sum are written out: as gol_conv4s2.h helpers they changed the VGPR counts of the
+// weight-gradient kernels, profiles/LOG.md "conv4s2")
 __global__ __launch_bounds__(256) void mvptail_bwd_w_kernel(int B, int h, int w, int CH, const float* __restrict__ px,
                                                             const float* __restrict__ pg, float* __restrict__ pscratch) {
-  __shared__ __attribute__((aligned(16))) float s_mem[16 * kGPlane + 16 * kXRow];
+  __shared__ __attribute__((aligned(16))) float s_mem[16 * kWinPlane + 16 * kPixRow];
   float* s_g = s_mem;
-  float* s_x = s_mem + 16 * kGPlane;
+  float* s_x = s_mem + 16 * kWinPlane;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, kq = lane >> 4;
   const int co0 = blockIdx.y * 16;
   const size_t HWi = (size_t)h * w, HWo = 4 * HWi;
@@ -357,7 +317,7 @@ __global__ __launch_bounds__(256) void mvptail_bwd_w_kernel(int B, int h, int w,
 #pragma unroll
     for (int u = 0; u < 4; ++u) rx[u] = xr[(size_t)(4 * u) * HWi];
     // one scalar base + 32-bit byte offsets inside the slab of <= 16 planes (planes hold < 2^26 floats)
-    const float* gs = mt_uniform(pg + ((size_t)b * CH + co0) * HWo);
+    const float* gs = gol_uniform(pg + ((size_t)b * CH + co0) * HWo);
 #pragma unroll
     for (int sgm = 0; sgm < 16; ++sgm) {
       const int seg = wave * 16 + sgm, oy = min(max(2 * iy - 1 + (seg & 3), 0), 2 * h - 1);
@@ -377,7 +337,7 @@ __global__ __launch_bounds__(256) void mvptail_bwd_w_kernel(int B, int h, int w,
     const int b = tile / (h * tpr), rem = tile - b * (h * tpr), iy = rem / tpr, ix0 = (rem - iy * tpr) * kWTile;
     const bool xv = ix0 + lane < w;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) s_x[(wave + 4 * u) * kXRow + lane] = xv ? rx[u] : 0.f;
+    for (int u = 0; u < 4; ++u) s_x[(wave + 4 * u) * kPixRow + lane] = xv ? rx[u] : 0.f;
 #pragma unroll
     for (int sgm = 0; sgm < 16; ++sgm) {
       const int seg = wave * 16 + sgm, pl = seg >> 2, dy = seg & 3, oy = 2 * iy - 1 + dy;
@@ -385,12 +345,12 @@ __global__ __launch_bounds__(256) void mvptail_bwd_w_kernel(int B, int h, int w,
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int cl = lane + 64 * u, col = 2 * ix0 - 1 + cl;
-        s_g[pl * kGPlane + dy * kGRow + cl] = (rv && col >= 0 && col < 2 * w) ? rg[2 * sgm + u] : 0.f;
+        s_g[pl * kWinPlane + dy * kWinRow + cl] = (rv && col >= 0 && col < 2 * w) ? rg[2 * sgm + u] : 0.f;
       }
     }
     if (tid < 128) {
       const int pl = lseg >> 2, dy = lseg & 3, oy = 2 * iy - 1 + dy, col = 2 * ix0 - 1 + lcl;
-      s_g[pl * kGPlane + dy * kGRow + lcl] = (co0 + pl < CH && oy >= 0 && oy < 2 * h && col < 2 * w) ? rlg : 0.f;
+      s_g[pl * kWinPlane + dy * kWinRow + lcl] = (co0 + pl < CH && oy >= 0 && oy < 2 * h && col < 2 * w) ? rlg : 0.f;
     }
   };
   // a workgroup takes a run of consecutive tiles (consecutive input rows re-read two of their four window rows)
@@ -403,11 +363,11 @@ __global__ __launch_bounds__(256) void mvptail_bwd_w_kernel(int B, int h, int w,
     __syncthreads();
     if (tile + 1 < t1) issue(tile + 1);
     const int xl = wave * 16 + 4 * kq;  // this lane's 4 input pixels (K slice) inside the tile
-    const float4 xa4 = *reinterpret_cast<const float4*>(&s_x[l15 * kXRow + xl]);
+    const float4 xa4 = *reinterpret_cast<const float4*>(&s_x[l15 * kPixRow + xl]);
     const float xa[4] = {xa4.x, xa4.y, xa4.z, xa4.w};
 #pragma unroll
     for (int dy = 0; dy < 4; ++dy) {
-      const float* gp = &s_g[l15 * kGPlane + dy * kGRow + 2 * xl];  // column 0 of s_g is global column 2 ix0 - 1
+      const float* gp = &s_g[l15 * kWinPlane + dy * kWinRow + 2 * xl];  // column 0 of s_g is global column 2 ix0 - 1
       float gv[10];
 #pragma unroll
       for (int q = 0; q < 10; q += 2) {
@@ -439,32 +399,17 @@ __global__ __launch_bounds__(256) void mvptail_bwd_w_kernel(int B, int h, int w,
     }
     __syncthreads();
   }
-  float* dst = pscratch + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16) * 256 + tid;
-#pragma unroll
-  for (int tap = 0; tap < 16; ++tap) dst[(size_t)tap * 256] = s_red[tap][tid];
+  wgrad_store_partial(pscratch + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16) * 256 + tid, s_red);
 }
 
-// gw[ci,ch,tap] = sum over the K blocks, written once.  grid (16 taps x 16 ci rows, channel tiles): a workgroup owns 16
-// outputs and sums them as 16 interleaved K slices that meet in LDS in slice order (cf. trunk_bwd_w_reduce_kernel)
+// gw[ci,ch,tap] = sum over the K blocks, written once.  grid (16 taps x 16 ci rows, channel tiles)
 __global__ __launch_bounds__(256) void mvptail_bwd_w_reduce_kernel(int CH, int nblk, const float* __restrict__ scratch,
                                                                    float* __restrict__ gw) {
-  __shared__ float s_part[16][16];
-  const int tap = blockIdx.x >> 4, ci = blockIdx.x & 15, col = threadIdx.x & 15, ks = threadIdx.x >> 4;
+  const int tap = blockIdx.x >> 4, ci = blockIdx.x & 15, col = threadIdx.x & 15;
   const int ch = blockIdx.y * 16 + col;
-  const float* src = scratch + (((size_t)blockIdx.y * nblk) * 16 + tap) * 256 + ci * 16 + col;
-  float acc = 0.f;
-#pragma unroll 4
-  for (int k = ks; k < nblk; k += 16) acc += src[(size_t)k * 16 * 256];
-  s_part[ks][col] = acc;
-  __syncthreads();
-  if (ks == 0 && ch < CH) {
-#pragma unroll
-    for (int q = 1; q < 16; ++q) acc += s_part[q][col];
-    gw[((size_t)ci * CH + ch) * 16 + tap] = acc;
-  }
+  wgrad_reduce16(scratch + (((size_t)blockIdx.y * nblk) * 16 + tap) * 256 + ci * 16 + col, nblk,
+                 gw + ((size_t)ci * CH + ch) * 16 + tap, ch < CH);
 }
-
-bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 int check_common(const char* who, int B, int Ci, int h, int w, int TD, int TH, int TW, int ny, int nx, int Kout) {
   if (Ci != kCi || TD < 1 || TD > kMaxTD) {
@@ -480,11 +425,8 @@ int check_common(const char* who, int B, int Ci, int h, int w, int TD, int TH, i
   return GOL_OK;
 }
 
-int bwd_w_blocks(int B, int h, int w, int ntile_ch) {
-  const long long ntiles = (long long)B * h * gol_cdiv(w, kWTile);
-  long long nblk = gol_cdiv(512, ntile_ch);  // two workgroups per CU: one round of them
-  nblk = nblk > ntiles ? ntiles : nblk;
-  return (int)(nblk < 1 ? 1 : nblk);
+int bwd_w_blocks(int B, int h, int w, int ntile_ch) {  // two workgroups per CU: one round of them
+  return wgrad_blocks((long long)B * h * gol_cdiv(w, kWTile), ntile_ch, 512);
 }
 
 // scratch: g_pre of the colours [B,3TD,Sy,Sx] (C == 4), g_pre of alpha [B,TD,Sy,Sx], then the weight gradient's partials
@@ -514,7 +456,7 @@ extern "C" int gol_mvp_tail_fwd(int B, int Ci, int h, int w, int TD, int TH, int
   if (B == 0 || Kout == 0) return GOL_OK;
   GOL_REQUIRE(x_alpha && w_alpha && bias_alpha && out, "null pointer");
   GOL_REQUIRE(!x_rgb || (w_rgb && bias_rgb), "x_rgb needs w_rgb and bias_rgb");
-  GOL_REQUIRE(!x_rgb || aligned16(out), "the four-channel template must be 16-byte aligned");
+  GOL_REQUIRE(!x_rgb || gol_aligned16(out), "the four-channel template must be 16-byte aligned");
   const MvpTailDims p{B, h, w, TD, TH, TW, ny, nx, Kout, rgb_scale, rgb_shift};
   hipStream_t s = (hipStream_t)stream;
   const int ntiles = (h + 1) * gol_cdiv(w + 1, 16);
@@ -559,7 +501,7 @@ extern "C" int gol_mvp_tail_bwd(int B, int Ci, int h, int w, int TD, int TH, int
     return GOL_OK;
   }
   GOL_REQUIRE(out, "null pointer");
-  GOL_REQUIRE(C == 1 || (aligned16(g_out) && aligned16(out)), "the four-channel g_out and out must be 16-byte aligned");
+  GOL_REQUIRE(C == 1 || (gol_aligned16(g_out) && gol_aligned16(out)), "the four-channel g_out and out must be 16-byte aligned");
   const bool slab_rgb = g_x_rgb || g_w_rgb, slab_alpha = g_x_alpha || g_w_alpha;
   GOL_REQUIRE(!(slab_rgb || slab_alpha) || scratch, "g_x and g_w need scratch");
   GOL_REQUIRE(!g_x_rgb || w_rgb_t, "g_x_rgb needs w_rgb_t");

@@ -17,13 +17,12 @@
 //           g[ch,pix'] -> v_mfma_f32_16x16x4_f32 (exact fp32), K = 4 input pixels per instruction,
 //           16 accumulator tiles (one per tap) per wave, LDS reduction over the 4 waves, then atomics;
 //   bwd_b   bias gradient: contracted planes  gbias[k] = sum_{b,e} lc[k,b,e] g[b,e], direct planes sum_b g.
-#include "gol_common.h"
+#include "gol_conv4s2.h"
 
 namespace {
 
 constexpr int kCi = 16;    // input channels of the last decoder layers (rgca.py:427,455)
 constexpr int kMaxB = 8;   // views per pass of the bias contraction (register budget)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // sizes travel in a struct, pointers as __restrict__ kernel parameters: only then can the compiler prove that the
 // stores to `out` / the gradients do not clobber the weights and coefficients, and fetch those wave-uniform
@@ -179,38 +178,9 @@ __global__ __launch_bounds__(256) void tail_conv_fwd_kernel(TAIL_FWD_ARGS) {
                       const float* __restrict__ plc, const float* __restrict__ pg, float* __restrict__ pgx, \
                       float* __restrict__ pgw, float* __restrict__ pgbias, float* __restrict__ pscratch
 
-// gx[b,ci,iy,ix] = sum_{ch,dy,dx} g[b,ch,2iy-1+dy,2ix-1+dx] * w[b,ci,ch,dy,dx];  wt = w as [wB,CH,4,4,16]
+// gx: the scalar gather of gol_conv4s2.h with this view's weights; wt = w as [wB,CH,4,4,16]
 __global__ __launch_bounds__(256) void tail_conv_bwd_x_kernel(TAIL_BWD_ARGS) {
-  const int ix = blockIdx.x * 256 + threadIdx.x, iy = blockIdx.y, b = blockIdx.z;
-  const int h = p.h, w = p.w, CH = p.CH;
-  if (ix >= w) return;
-  const size_t HWi = (size_t)h * w, HWo = 4 * HWi;
-  const float* wt = pwt + (size_t)(p.wB == 1 ? 0 : b) * CH * 256;
-  const float* gb = pg + (size_t)b * CH * HWo;
-  float acc[kCi];
-#pragma unroll
-  for (int ci = 0; ci < kCi; ++ci) acc[ci] = 0.f;
-#pragma unroll
-  for (int dy = 0; dy < 4; ++dy) {
-    const int oy = 2 * iy - 1 + dy;
-    if (oy < 0 || oy >= 2 * h) continue;  // block-uniform
-    const int ox0 = 2 * ix - 1;
-    const bool ok0 = ox0 >= 0, ok3 = ox0 + 3 < 2 * w;
-    for (int ch = 0; ch < CH; ++ch) {
-      const float* gr = gb + (size_t)ch * HWo + (size_t)oy * (2 * w) + ox0;
-      float gv[4];  // unconditional loads (edge lanes re-read a neighbour), then masked: no divergent branches
-      gv[0] = gr[ok0 ? 0 : 1]; gv[1] = gr[1]; gv[2] = gr[2]; gv[3] = gr[ok3 ? 3 : 2];
-      gv[0] = ok0 ? gv[0] : 0.f; gv[3] = ok3 ? gv[3] : 0.f;
-#pragma unroll
-      for (int dx = 0; dx < 4; ++dx) {
-        const float* wq = wt + ((size_t)(ch * 4 + dy) * 4 + dx) * 16;  // wave-uniform
-#pragma unroll
-        for (int ci = 0; ci < kCi; ++ci) acc[ci] += gv[dx] * wq[ci];
-      }
-    }
-  }
-#pragma unroll
-  for (int ci = 0; ci < kCi; ++ci) pgx[((size_t)b * kCi + ci) * HWi + (size_t)iy * w + ix] = acc[ci];
+  gather_bwd_x16(p.h, p.w, p.CH, pwt + (size_t)(p.wB == 1 ? 0 : blockIdx.z) * p.CH * 256, pg, pgx);
 }
 
 // gw[b,ci,ch,dy,dx] += sum_{iy,ix} x[b,ci,iy,ix] * g[b,ch,2iy-1+dy,2ix-1+dx]
@@ -218,15 +188,12 @@ __global__ __launch_bounds__(256) void tail_conv_bwd_x_kernel(TAIL_BWD_ARGS) {
 // [16 ch][4 rows][130 cols] are staged in LDS with coalesced loads; each of the 4 waves then feeds its 16-pixel
 // chunk to 64 MFMAs (16 taps x K = 16 pixels / 4 per instruction).  A[i = ci][k], B[k][j = ch] operands come from
 // LDS in the (lane&15, lane>>4) layout the instruction wants.
-constexpr int kWTile = 64;
-constexpr int kGRow = 2 * kWTile + 4;     // 130 used
-constexpr int kGPlane = 4 * kGRow + 2;    // == 2 (mod 32): the 16 planes of a lane group spread over the banks
-constexpr int kXRow = kWTile + 4;         // == 4 (mod 32)
-
+// (the loaders, the MFMA nest and the wave sum are written out: as gol_conv4s2.h helpers they changed the VGPR counts of the
+// weight-gradient kernels, profiles/LOG.md "conv4s2")
 __global__ __launch_bounds__(256) void tail_conv_bwd_w_kernel(TAIL_BWD_ARGS) {
-  __shared__ __attribute__((aligned(16))) float s_mem[16 * kGPlane + 16 * kXRow];
+  __shared__ __attribute__((aligned(16))) float s_mem[16 * kWinPlane + 16 * kPixRow];
   float* s_g = s_mem;
-  float* s_x = s_mem + 16 * kGPlane;
+  float* s_x = s_mem + 16 * kWinPlane;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.z, nt = blockIdx.y;
   const int h = p.h, w = p.w, CH = p.CH;
@@ -266,7 +233,7 @@ __global__ __launch_bounds__(256) void tail_conv_bwd_w_kernel(TAIL_BWD_ARGS) {
   auto stage = [&](int tile) {  // registers -> LDS, out-of-range elements as zeros
     const int iy = tile / tpr, ix0 = (tile - iy * tpr) * kWTile;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) s_x[xci * kXRow + xj4 + u] = (ix0 + xj4 + u < w) ? rx[u] : 0.f;
+    for (int u = 0; u < 4; ++u) s_x[xci * kPixRow + xj4 + u] = (ix0 + xj4 + u < w) ? rx[u] : 0.f;
 #pragma unroll
     for (int sgm = 0; sgm < 16; ++sgm) {
       const int seg = wave * 16 + sgm, pl = seg >> 2, dy = seg & 3, oy = 2 * iy - 1 + dy;
@@ -274,13 +241,13 @@ __global__ __launch_bounds__(256) void tail_conv_bwd_w_kernel(TAIL_BWD_ARGS) {
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int cl = lane + 64 * u, col = 2 * ix0 - 1 + cl;
-        s_g[pl * kGPlane + dy * kGRow + cl] = (rv && col >= 0 && col < 2 * w) ? rg[2 * sgm + u] : 0.f;
+        s_g[pl * kWinPlane + dy * kWinRow + cl] = (rv && col >= 0 && col < 2 * w) ? rg[2 * sgm + u] : 0.f;
       }
     }
     if (threadIdx.x < 128) {
       const int pl = lseg >> 2, dy = lseg & 3, oy = 2 * iy - 1 + dy, col = 2 * ix0 - 1 + lcl;
       const bool rv = nt * 16 + pl < CH && oy >= 0 && oy < 2 * h && col < 2 * w;
-      s_g[pl * kGPlane + dy * kGRow + lcl] = rv ? rl : 0.f;
+      s_g[pl * kWinPlane + dy * kWinRow + lcl] = rv ? rl : 0.f;
     }
   };
   if ((int)blockIdx.x < ntiles) issue(blockIdx.x);
@@ -290,16 +257,16 @@ __global__ __launch_bounds__(256) void tail_conv_bwd_w_kernel(TAIL_BWD_ARGS) {
     __syncthreads();
     if (tile + (int)gridDim.x < ntiles) issue(tile + gridDim.x);
     const int xl = 16 * wave + 4 * kq;  // this lane's 4 input pixels (K slice) inside the tile
-    const float4 xa4 = *reinterpret_cast<const float4*>(&s_x[l15 * kXRow + xl]);
+    const float4 xa4 = *reinterpret_cast<const float4*>(&s_x[l15 * kPixRow + xl]);
     const float xa[4] = {xa4.x, xa4.y, xa4.z, xa4.w};
 #pragma unroll
     for (int dy = 0; dy < 4; ++dy) {
-      const float* gp = &s_g[l15 * kGPlane + dy * kGRow + 2 * xl];  // column 0 of s_g is global column 2*ix0-1
+      const float* gp = &s_g[l15 * kWinPlane + dy * kWinRow + 2 * xl];  // column 0 of s_g is global column 2 ix0 - 1
       float gv[10];
 #pragma unroll
       for (int q = 0; q < 10; q += 2) {
-        const float2 t = *reinterpret_cast<const float2*>(gp + q);
-        gv[q] = t.x; gv[q + 1] = t.y;
+        const float2 t2 = *reinterpret_cast<const float2*>(gp + q);
+        gv[q] = t2.x; gv[q + 1] = t2.y;
       }
 #pragma unroll
       for (int dx = 0; dx < 4; ++dx)
@@ -329,9 +296,7 @@ __global__ __launch_bounds__(256) void tail_conv_bwd_w_kernel(TAIL_BWD_ARGS) {
     // per-workgroup partials [B][NT][NBLK][16 taps][256 = ci*16 + ch_local], summed by tail_conv_bwd_w_reduce_kernel:
     // hundreds of workgroups adding to the same few thousand addresses with memory-side float atomics cost up to
     // half of this kernel
-    float* dst = pscratch + ((((size_t)b * gridDim.y + nt) * gridDim.x + blockIdx.x) * 16) * 256 + threadIdx.x;
-#pragma unroll
-    for (int tap = 0; tap < 16; ++tap) dst[(size_t)tap * 256] = s_red[tap][threadIdx.x];
+    wgrad_store_partial(pscratch + ((((size_t)b * gridDim.y + nt) * gridDim.x + blockIdx.x) * 16) * 256 + threadIdx.x, s_red);
     return;
   }
   const int ci = threadIdx.x >> 4, cj = nt * 16 + (threadIdx.x & 15);
@@ -449,10 +414,8 @@ extern "C" int gol_tail_conv_fwd(int B, int Ci, int h, int w, int CH, int E, int
   return GOL_OK;
 }
 
-static int bwd_w_blocks(int B, int h, int w, int CH) {
-  const int ntiles = h * gol_cdiv(w, kWTile), ntile_ch = gol_cdiv(CH, 16);
-  int nblk = gol_cdiv(768, (long long)ntile_ch * (B > 0 ? B : 1));  // ~3 workgroups per CU
-  return nblk < 1 ? 1 : (nblk > ntiles ? ntiles : nblk);
+static int bwd_w_blocks(int B, int h, int w, int CH) {  // ~3 workgroups per CU
+  return wgrad_blocks(h * gol_cdiv(w, kWTile), (long long)gol_cdiv(CH, 16) * (B > 0 ? B : 1), 768);
 }
 
 extern "C" long long gol_tail_conv_bwd_scratch_floats(int B, int h, int w, int CH) {

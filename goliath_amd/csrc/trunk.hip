@@ -3,39 +3,22 @@
 // The reference stacks six ConvTranspose2dWNUB(Ci -> Co, k4 s2 p1) + untied bias + LeakyReLU in front of each last
 // decoder layer (/root/reference/ca_code/models/rgca.py:408-426,429-454; ca_code/nn/layers.py:331-397,157-244):
 //     y[b,co,Y,X] = lrelu( sum_{ci,ky,kx} x[b,ci,iy,ix] W[ci,co,ky,kx] + bias[co,Y,X] ),   Y = 2 iy - 1 + ky
-// run there as a MIOpen convolution, an ATen add and an ATen leaky_relu (and five kernels backward).  Here:
-//   fwd     the tail.hip formulation: the output 2x2 quad {2m-1, 2m} x {2k-1, 2k} reads the 2x2 input block
-//           {m-1, m} x {k-1, k} and uses each of the 16 taps once, so every output parity class (a,q) is a GEMM
-//           D[co][quad] = A[co][(ci,tap)] B[(ci,tap)][quad] on v_mfma_f32_16x16x4_f32 (exact fp32, K = the 4 taps
-//           of one ci).  B is shared by the four classes.  Weights go through an LDS tile per K stage of 8 input
-//           channels; bias + LeakyReLU happen on the accumulators; nothing but y is written.
+// run there as a MIOpen convolution, an ATen add and an ATen leaky_relu (and five kernels backward).  Here, in the three
+// formulations of gol_conv4s2.h (coarse grid = x, fine grid = y):
+//   fwd     quad form, reduction over ci in K stages of 8; bias + LeakyReLU happen on the accumulators; nothing but y is
+//           written.
 //   bwd     g_pre = g_y (y > 0 ? 1 : leak) is formed while loading (leak > 0 keeps the sign, so y carries the mask):
-//     bwd_x   gather form, no atomics: D[ci][pixel] += A[ci][ky] B[ky][pixel] per (co, kx), K = the 4 rows of the
-//             window, so a lane's four kx come from one 16-byte load;
-//     bwd_w   per (16 ci x 16 co) tile pair a GEMM over pixels, 16 accumulator tiles (one per tap), staged and
-//             pipelined as tail_conv_bwd_w_kernel, up to four ci tiles sharing a staged g_pre window; K is split over
-//             workgroups, partial sums go to scratch, a second kernel adds them in a fixed order (no float atomics:
-//             bitwise reproducible);
+//     bwd_x   row gather, reduction over co in K stages of 4, weights pre-permuted by the caller;
+//     bwd_w   weight gradient per (16 ci x 16 co) tile pair, up to four ci tiles sharing a staged g_pre window;
 //     bwd_b   g_bias[co,Y,X] = sum_b g_pre, one streaming pass.
-#include "gol_common.h"
+#include "gol_conv4s2.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct TrunkDims {
   int B, Ci, Co, h, w;
   float leak;
 };
-
-// a wave-uniform pointer pinned to SGPRs: loads through gol_at(gol_uniform(base), lane_offset) take the scalar-base +
-// 32-bit lane-offset form (otherwise the loop-invariant lane part is folded into a 64-bit per-lane base: 2 VGPRs per load)
-template <typename T>
-__device__ __forceinline__ T* gol_uniform(T* q) {
-  const uint64_t v = reinterpret_cast<uint64_t>(q);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return reinterpret_cast<T*>(((uint64_t)hi << 32) | lo);
-}
 
 constexpr int kFwdKC = 8;  // input channels per K stage of the forward (Ci is a multiple of 8)
 constexpr int kBxKC = 4;   // output channels per K stage of the input gradient (Co is a multiple of 16)
@@ -46,6 +29,8 @@ constexpr int kBxKC = 4;   // output channels per K stage of the input gradient 
 // One wave = 16 quads (linear over the (h+1) x (w+1) quad grid, so narrow layers fill their tiles) x 16 CT channels x
 // 4 classes = 4 CT independent accumulators.  MFMA operands: A[i = lane & 15][k = lane >> 4], B[k][j = lane & 15],
 // D[i = 4 (lane >> 4) + r][j].
+// (written out, not a gol_conv4s2.h helper: as quad_gemm + callbacks, shared with enc_bwd_x_kernel, the epilogue's
+// address arithmetic grew by 20-68 instructions per instance: profiles/LOG.md "conv4s2")
 template <int CT>
 __global__ __launch_bounds__(256) void trunk_fwd_kernel(const TrunkDims p, const float* __restrict__ px,
                                                         const float* __restrict__ pw, const float* __restrict__ pbias,
@@ -144,8 +129,8 @@ __global__ __launch_bounds__(256) void trunk_fwd_kernel(const TrunkDims p, const
 // wt = W as [Co,4 kx,Ci,4 ky], so the A operand of (co, kx, 16 input channels) is 64 consecutive floats in memory and
 // in LDS (element 4 j + g).  grid (B, tiles of 64 input pixels, groups of 16 CT input channels); one wave = 16 pixels x
 // 16 CT channels, two accumulators per channel tile (even / odd kx).
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-
+// (written out, not a gol_conv4s2.h helper: as row_gemm + callbacks, shared with enc_fwd_kernel, the VGPR counts of
+// three instances moved or the loaded block spilled: profiles/LOG.md "conv4s2")
 template <int CT, bool WIDE>
 __global__ __launch_bounds__(256) void trunk_bwd_x_kernel(const TrunkDims p, const float* __restrict__ pwt,
                                                           const float* __restrict__ py, const float* __restrict__ pg,
@@ -247,19 +232,16 @@ __global__ __launch_bounds__(256) void trunk_bwd_x_kernel(const TrunkDims p, con
 // g_pre window [16 co][4 rows][130 cols] are staged in LDS; the window is shared by the NCI channel tiles (wave ->
 // channel tile wave % NCI, pixel part wave / NCI), each wave feeds 16-pixel chunks to 64 MFMAs (16 taps x 4 pixels per
 // instruction); the waves' sums meet in LDS and leave as one partial [16 taps][16 ci][16 co] per channel tile.
-constexpr int kWTile = 64;
-constexpr int kGRow = 2 * kWTile + 4;   // 130 used
-constexpr int kGPlane = 4 * kGRow + 2;  // == 2 (mod 32): the 16 planes of a lane group spread over the banks
-constexpr int kXRow = kWTile + 4;
-
+// (the loaders, the MFMA nest and the wave sum are written out: as gol_conv4s2.h helpers they changed the VGPR counts of the
+// weight-gradient kernels, profiles/LOG.md "conv4s2")
 template <int NCI>
 __global__ __launch_bounds__(256) void trunk_bwd_w_kernel(const TrunkDims p, const float* __restrict__ px,
                                                           const float* __restrict__ py, const float* __restrict__ pg,
                                                           float* __restrict__ pscratch) {
   constexpr int NP = 4 / NCI;  // waves that share a channel tile split the tile's 64 pixels
-  __shared__ __attribute__((aligned(16))) float s_mem[16 * kGPlane + NCI * 16 * kXRow];
+  __shared__ __attribute__((aligned(16))) float s_mem[16 * kWinPlane + NCI * 16 * kPixRow];
   float* s_g = s_mem;
-  float* s_x = s_mem + 16 * kGPlane;
+  float* s_x = s_mem + 16 * kWinPlane;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, kq = lane >> 4;
   const int cil = wave % NCI, part = wave / NCI;
   const int h = p.h, w = p.w, Ci = p.Ci, Co = p.Co;
@@ -310,7 +292,7 @@ __global__ __launch_bounds__(256) void trunk_bwd_w_kernel(const TrunkDims p, con
     // (channels past Ci hold a copy of a valid row: they only reach accumulator rows that the reduce kernel drops)
     const bool xv = ix0 + lane < w;
 #pragma unroll
-    for (int u = 0; u < 4 * NCI; ++u) s_x[(wave + 4 * u) * kXRow + lane] = xv ? rx[u] : 0.f;
+    for (int u = 0; u < 4 * NCI; ++u) s_x[(wave + 4 * u) * kPixRow + lane] = xv ? rx[u] : 0.f;
 #pragma unroll
     for (int sgm = 0; sgm < 16; ++sgm) {
       const int seg = wave * 16 + sgm, pl = seg >> 2, dy = seg & 3, oy = 2 * iy - 1 + dy;
@@ -318,13 +300,13 @@ __global__ __launch_bounds__(256) void trunk_bwd_w_kernel(const TrunkDims p, con
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int cl = lane + 64 * u, col = 2 * ix0 - 1 + cl;
-        s_g[pl * kGPlane + dy * kGRow + cl] =
+        s_g[pl * kWinPlane + dy * kWinRow + cl] =
             (rv && col >= 0 && col < 2 * w) ? rg[2 * sgm + u] * (ry[2 * sgm + u] > 0.f ? 1.f : leak) : 0.f;
       }
     }
     if (tid < 128) {
       const int pl = lseg >> 2, dy = lseg & 3, oy = 2 * iy - 1 + dy, col = 2 * ix0 - 1 + lcl;
-      s_g[pl * kGPlane + dy * kGRow + lcl] = (oy >= 0 && oy < 2 * h && col < 2 * w) ? rlg * (rly > 0.f ? 1.f : leak) : 0.f;
+      s_g[pl * kWinPlane + dy * kWinRow + lcl] = (oy >= 0 && oy < 2 * h && col < 2 * w) ? rlg * (rly > 0.f ? 1.f : leak) : 0.f;
     }
   };
   // A workgroup takes a run of consecutive tiles (consecutive input rows re-read two of their four g_pre rows), and the
@@ -341,11 +323,11 @@ __global__ __launch_bounds__(256) void trunk_bwd_w_kernel(const TrunkDims p, con
 #pragma unroll
     for (int c = 0; c < NCI; ++c) {
       const int xl = (part * NCI + c) * 16 + 4 * kq;  // this lane's 4 input pixels (K slice) inside the tile
-      const float4 xa4 = *reinterpret_cast<const float4*>(&s_x[(cil * 16 + l15) * kXRow + xl]);
+      const float4 xa4 = *reinterpret_cast<const float4*>(&s_x[(cil * 16 + l15) * kPixRow + xl]);
       const float xa[4] = {xa4.x, xa4.y, xa4.z, xa4.w};
 #pragma unroll
       for (int dy = 0; dy < 4; ++dy) {
-        const float* gp = &s_g[l15 * kGPlane + dy * kGRow + 2 * xl];  // column 0 of s_g is global column 2 ix0 - 1
+        const float* gp = &s_g[l15 * kWinPlane + dy * kWinRow + 2 * xl];  // column 0 of s_g is global column 2 ix0 - 1
         float gv[10];
 #pragma unroll
         for (int q = 0; q < 10; q += 2) {
@@ -379,59 +361,29 @@ __global__ __launch_bounds__(256) void trunk_bwd_w_kernel(const TrunkDims p, con
       }
       __syncthreads();
     }
-    float* dst = pscratch + ((((size_t)blockIdx.y * NCI + c) * gridDim.x + blockIdx.x) * 16) * 256 + tid;
-#pragma unroll
-    for (int tap = 0; tap < 16; ++tap) dst[(size_t)tap * 256] = s_red[tap][tid];
+    wgrad_store_partial(pscratch + ((((size_t)blockIdx.y * NCI + c) * gridDim.x + blockIdx.x) * 16) * 256 + tid, s_red);
     __syncthreads();
   }
 }
 
-// gw[ci,co,tap] = sum over the K blocks (written once).  grid (16 taps x 16 ci rows, channel tiles): a workgroup owns 16
-// outputs and sums them as 16 interleaved K slices that meet in LDS in slice order -- a fixed order, and 16 x the
-// workgroups and 1/16 of the dependent loads of one thread per output (hundreds of K blocks for a layer with few tiles)
+// gw[ci,co,tap] = sum over the K blocks (written once).  grid (16 taps x 16 ci rows, channel tiles)
 __global__ __launch_bounds__(256) void trunk_bwd_w_reduce_kernel(const TrunkDims p, int NCI, int nblk,
                                                                  const float* __restrict__ scratch,
                                                                  float* __restrict__ gw) {
-  __shared__ float s_part[16][16];
-  const int tap = blockIdx.x >> 4, row = blockIdx.x & 15, col = threadIdx.x & 15, ks = threadIdx.x >> 4;
+  const int tap = blockIdx.x >> 4, row = blockIdx.x & 15, col = threadIdx.x & 15;
   const int nco = p.Co >> 4, grp = blockIdx.y / NCI, c = blockIdx.y - grp * NCI;
   const int cig = grp / nco, cot = grp - cig * nco;
   const int ci = (cig * NCI + c) * 16 + row, co = cot * 16 + col;
   if (ci >= p.Ci) return;  // block-uniform: ragged last tile (Ci = 8 * odd) or a tile past the end of the last group
-  const float* src = scratch + (((size_t)blockIdx.y * nblk) * 16 + tap) * 256 + row * 16 + col;
-  float acc = 0.f;
-#pragma unroll 4
-  for (int k = ks; k < nblk; k += 16) acc += src[(size_t)k * 16 * 256];
-  s_part[ks][col] = acc;
-  __syncthreads();
-  if (ks == 0) {
-#pragma unroll
-    for (int q = 1; q < 16; ++q) acc += s_part[q][col];
-    gw[((size_t)ci * p.Co + co) * 16 + tap] = acc;
-  }
+  wgrad_reduce16(scratch + (((size_t)blockIdx.y * nblk) * 16 + tap) * 256 + row * 16 + col, nblk,
+                 gw + ((size_t)ci * p.Co + co) * 16 + tap, true);
 }
 
-// ---- bias gradient ---------------------------------------------------------------------------------------------------
-// gbias[n] = sum_b gpre[b,n] over the Co * 2h * 2w plane elements, four per thread
+// ---- bias gradient: over the Co * 2h * 2w plane elements, four per thread -----------------------------------------------
 __global__ __launch_bounds__(256) void trunk_bwd_b_kernel(const TrunkDims p, const float* __restrict__ py,
                                                           const float* __restrict__ pg, float* __restrict__ pgb) {
-  const size_t N4 = (size_t)p.Co * p.h * p.w;  // float4 count of one view
-  const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= N4) return;
-  const float leak = p.leak;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int b = 0; b < p.B; ++b) {
-    const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pg) + (size_t)b * N4 + n);
-    const f32x4 yv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(py) + (size_t)b * N4 + n);
-    s.x += gv.x * (yv.x > 0.f ? 1.f : leak);
-    s.y += gv.y * (yv.y > 0.f ? 1.f : leak);
-    s.z += gv.z * (yv.z > 0.f ? 1.f : leak);
-    s.w += gv.w * (yv.w > 0.f ? 1.f : leak);
-  }
-  reinterpret_cast<float4*>(pgb)[n] = s;
+  lrelu_bias_grad((size_t)p.Co * p.h * p.w, p.B, p.leak, py, pg, pgb);
 }
-
-bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 int check_common(int B, int Ci, int Co, int h, int w, float leak) {
   GOL_REQUIRE(B >= 0 && Ci > 0 && Co > 0 && h > 0 && w > 0, "bad sizes");
@@ -453,11 +405,9 @@ int check_common(int B, int Ci, int Co, int h, int w, float leak) {
 int bwd_w_nci(int Ci) { return Ci > 32 ? 4 : (Ci > 16 ? 2 : 1); }
 int bwd_w_groups(int Ci, int Co) { return gol_cdiv(Ci, 16 * bwd_w_nci(Ci)) * (Co / 16); }
 
+// 2 workgroups per CU are resident (registers): one round of them
 int bwd_w_blocks(int B, int Ci, int Co, int h, int w) {
-  const long long ntiles = (long long)B * h * gol_cdiv(w, kWTile), pairs = bwd_w_groups(Ci, Co);
-  long long nblk = (512 + pairs - 1) / pairs;  // 2 workgroups per CU are resident (registers): one round of them
-  nblk = nblk > ntiles ? ntiles : nblk;
-  return (int)(nblk < 1 ? 1 : nblk);
+  return wgrad_blocks((long long)B * h * gol_cdiv(w, kWTile), bwd_w_groups(Ci, Co), 512);
 }
 
 }  // namespace
@@ -468,7 +418,7 @@ extern "C" int gol_trunk_conv_fwd(int B, int Ci, int Co, int h, int w, float lea
   if (rc != GOL_OK) return rc;
   if (B == 0) return GOL_OK;
   GOL_REQUIRE(x && w_eff && bias && y, "null pointer");
-  GOL_REQUIRE(aligned16(w_eff), "w_eff must be 16-byte aligned");
+  GOL_REQUIRE(gol_aligned16(w_eff), "w_eff must be 16-byte aligned");
   const TrunkDims p{B, Ci, Co, h, w, leak};
   hipStream_t s = (hipStream_t)stream;
   const int tiles = gol_cdiv((long long)(h + 1) * (w + 1), 64);
@@ -495,9 +445,9 @@ extern "C" int gol_trunk_conv_bwd(int B, int Ci, int Co, int h, int w, float lea
     return GOL_OK;
   }
   GOL_REQUIRE(y && g_y, "null pointer");
-  GOL_REQUIRE(!g_x || (w_eff_t && aligned16(w_eff_t)), "g_x needs w_eff_t (16-byte aligned)");
+  GOL_REQUIRE(!g_x || (w_eff_t && gol_aligned16(w_eff_t)), "g_x needs w_eff_t (16-byte aligned)");
   GOL_REQUIRE(!g_w || (x && scratch), "g_w needs x and scratch");
-  GOL_REQUIRE(!g_bias || (aligned16(y) && aligned16(g_y) && aligned16(g_bias)), "g_bias needs 16-byte aligned y, g_y, g_bias");
+  GOL_REQUIRE(!g_bias || (gol_aligned16(y) && gol_aligned16(g_y) && gol_aligned16(g_bias)), "g_bias needs 16-byte aligned y, g_y, g_bias");
   const TrunkDims p{B, Ci, Co, h, w, leak};
   if (g_x) {
     const int tiles = gol_cdiv((long long)h * w, 64);
