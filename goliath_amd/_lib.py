@@ -44,6 +44,7 @@ _SYMBOLS = [
     "gol_normal_rgba",
     "gol_olat_features_fwd", "gol_olat_combine_fwd", "gol_olat_combine_bwd",
     "gol_mvp_tail_fwd", "gol_mvp_tail_bwd_scratch_floats", "gol_mvp_tail_bwd",
+    "gol_conv3_fwd", "gol_conv3_bwd_x",
 ]
 
 

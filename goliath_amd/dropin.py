@@ -547,15 +547,18 @@ REGULARIZER_LOSSES = ("bound_primscale", "negcolor", "l2_reg", "list_l1_reg", "b
 IMAGE_LOSSES = ("rgb_l2", "psnr", "rgb_l1_focus", "rgb_l1_phys", "pose_shadow_l2")
 
 
-def patch_losses(registry_module=None, regularizers=False, images=False):
+def patch_losses(registry_module=None, regularizers=False, images=False, perceptual=None):
     """Re-register the image losses of the reference's loss registry (ca_code/loss/registry.py:59-79; rgb_l1 and
     rgb_ssim, ca_code/loss/__init__.py:391-411, 478-494) with the fused HIP versions, so a `ModularLoss` built from the
     unchanged config picks them up.  Call after `import ca_code.loss` and before constructing the loss.
     regularizers=True also re-registers the per-Gaussian regularisers and their kin (REGULARIZER_LOSSES,
     ca_code/loss/__init__.py:450-453, 560-600, 609-622) with the gol_regloss_* / gol_backlit_* operators of
     goliath_amd.losses; images=True also re-registers the L2 / focus image losses (IMAGE_LOSSES,
-    ca_code/loss/__init__.py:366-386, 415-445, 496-538, 555-557) with the gol_imgloss_* operators.  Every other entry of the
-    registry stays the reference's."""
+    ca_code/loss/__init__.py:366-386, 415-445, 496-538, 555-557) with the gol_imgloss_* operators.  perceptual= a
+    torchvision vgg19 state dict, the path of one or a goliath_amd.perceptual.Vgg19Features also re-registers `vgg`
+    (ca_code/loss/perceptual.py:55-58) with goliath_amd.perceptual.VGGLoss over that network (gol_conv3_* where the layer's
+    shape is in perceptual.DISPATCH); the weights come from the caller, nothing is downloaded, and the default (None)
+    leaves `vgg` untouched.  Every other entry of the registry (effnet, effnet_phys among them) stays the reference's."""
     from . import losses
 
     if registry_module is None:
@@ -573,6 +576,12 @@ def patch_losses(registry_module=None, regularizers=False, images=False):
     if images:
         for name in IMAGE_LOSSES:
             registry_module.loss_registry[name] = factory(getattr(losses, name))
+    if perceptual is not None:
+        from . import perceptual as perceptual_module
+
+        features = perceptual_module.as_features(perceptual)
+        registry_module.loss_registry["vgg"] = \
+            lambda assets=None, **kwargs: perceptual_module.VGGLoss(assets, features=features, **kwargs)
     return registry_module
 
 

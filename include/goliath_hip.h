@@ -625,6 +625,40 @@ int gol_upconv_bwd(int B, int Ci, int Co, int Hi, int Wi, int mode, float leak, 
                    float* g_bias, float* g_gate, float* g_gb, float* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * gol_conv3_fwd / gol_conv3_bwd_x: a layer of the frozen VGG19 feature network of the masked perceptual loss
+ * (ca_code/loss/vgg.py:17-88; `vgg`, ca_code/loss/perceptual.py:55-58) as one operator: 3x3 / stride 1 / zero padding 1
+ * convolution + bias + ReLU, optionally on the normalised image and optionally followed by the 2x2 max-pool.  Replaces
+ * the MIOpen convolution, the ATen bias add, relu, max_pool2d and the normalisation passes.  fp32 MFMA
+ * (v_mfma_f32_16x16x4_f32), exact fp32.
+ *   x [B,Ci,H,W]; weight [Co,Ci,3,3]; bias [Co]; y [B,Co,H,W], or with pool p [B,Co,H/2,W/2] and pos (bytes) of p's shape.
+ *   acc[b,co,r,c] = sum_{ci,ky,kx} xpad[b,ci,r-1+ky,c-1+kx] weight[co,ci,ky,kx]         (xpad = x inside the image, 0 outside)
+ *   y = relu(acc + bias[co])
+ * image_in (Ci == 3): the operand is n = (clamp(x / 255.f, 0, 1) - mean_c) / std_c, formed while loading, with
+ *   mean = (0.485, 0.456, 0.406), std = (0.229, 0.224, 0.225) (vgg.py:62-65): IEEE division, that operation order, no
+ *   contraction, so x = 255 gives exactly 1.  The zero padding is zero in NORMALISED space: a pixel outside the image
+ *   contributes 0, not (0 - mean) / std.  K = 27 is padded to 28.
+ * pool (2x2 max, stride 2, floor): only p and pos are written; y never exists.  pos is the window position of the maximum,
+ *   0..3 row-major; the first maximum in that order wins a tie.  A last odd row or column feeds nothing.  Tiles have an
+ *   even origin and an even size, so no window straddles workgroups.  H < 2 or W < 2 with pool: GOL_ERR_UNSUPPORTED.
+ * gol_conv3_bwd_x: the input gradient only (the weights are frozen).  y = the forward's y, or p with pool (then g_y is g_p
+ *   [B,Co,H/2,W/2] and pos the forward's bytes).  g_pre is formed while loading:
+ *     without pool  g_pre = g_y where y > 0, else 0
+ *     with pool     g_pre[r,c] = g_p[r/2,c/2] where pos names (r,c) and p > 0, else 0: a window whose maximum is 0 passes
+ *                   nothing, a row or column dropped by the floor receives 0
+ *   g_x [B,Ci,H,W] written = the transposed 3x3 convolution of g_pre, read from the same weight with mirrored taps (no
+ *   flipped copy).  image_in: g_x is the gradient of the IMAGE, g_n / std_c / 255 where 0 <= x / 255 <= 1 (edges inclusive,
+ *   as torch's clamp backward), else 0; needs x; Ci = 3 runs as a 16-row tile with zero weights.  Without image_in x may
+ *   be NULL.  No atomics, no scratch: bitwise reproducible.
+ * Supported: Ci == 3 with image_in, Ci % 8 == 0 without; Co % 16 == 0; any H, W >= 1; B <= 65535: everything else returns
+ * GOL_ERR_UNSUPPORTED.  A null pointer with positive sizes returns GOL_ERR_INVALID_ARG; B == 0 returns GOL_OK without a
+ * launch.  No host sync, no allocation: one launch each, capturable as a linear graph.
+ * ---------------------------------------------------------------------------------------- */
+int gol_conv3_fwd(int B, int Ci, int Co, int H, int W, int image_in, int pool, const float* x, const float* weight,
+                  const float* bias, float* y, unsigned char* pos, void* stream);
+int gol_conv3_bwd_x(int B, int Ci, int Co, int H, int W, int image_in, int pool, const float* x, const float* weight,
+                    const float* y, const unsigned char* pos, const float* g_y, float* g_x, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * SSIM image loss ("next" row).  Replaces `ssim` / `_ssim`
  * (ca_code/utils/ssim.py:25-65) as used by rgb_ssim (ca_code/loss/__init__.py:478-494): 11x11 Gaussian
  * window (sigma 1.5, zero padding), C1 = 0.01^2, C2 = 0.03^2, masked mean.
