@@ -45,6 +45,7 @@ _SYMBOLS = [
     "gol_olat_features_fwd", "gol_olat_combine_fwd", "gol_olat_combine_bwd",
     "gol_mvp_tail_fwd", "gol_mvp_tail_bwd_scratch_floats", "gol_mvp_tail_bwd",
     "gol_conv3_fwd", "gol_conv3_bwd_x",
+    "gol_mbconv_front_tiles", "gol_mbconv_front_fwd", "gol_mbconv_front_bwd_x",
 ]
 
 

@@ -547,7 +547,7 @@ REGULARIZER_LOSSES = ("bound_primscale", "negcolor", "l2_reg", "list_l1_reg", "b
 IMAGE_LOSSES = ("rgb_l2", "psnr", "rgb_l1_focus", "rgb_l1_phys", "pose_shadow_l2")
 
 
-def patch_losses(registry_module=None, regularizers=False, images=False, perceptual=None):
+def patch_losses(registry_module=None, regularizers=False, images=False, perceptual=None, effnet=None):
     """Re-register the image losses of the reference's loss registry (ca_code/loss/registry.py:59-79; rgb_l1 and
     rgb_ssim, ca_code/loss/__init__.py:391-411, 478-494) with the fused HIP versions, so a `ModularLoss` built from the
     unchanged config picks them up.  Call after `import ca_code.loss` and before constructing the loss.
@@ -558,7 +558,12 @@ def patch_losses(registry_module=None, regularizers=False, images=False, percept
     torchvision vgg19 state dict, the path of one or a goliath_amd.perceptual.Vgg19Features also re-registers `vgg`
     (ca_code/loss/perceptual.py:55-58) with goliath_amd.perceptual.VGGLoss over that network (gol_conv3_* where the layer's
     shape is in perceptual.DISPATCH); the weights come from the caller, nothing is downloaded, and the default (None)
-    leaves `vgg` untouched.  Every other entry of the registry (effnet, effnet_phys among them) stays the reference's."""
+    leaves `vgg` untouched.  effnet= a torchvision efficientnet_b0 state dict, the path of one or a
+    goliath_amd.effnet.EffNetB0Features also re-registers `effnet` and `effnet_phys` (ca_code/loss/perceptual.py:61-69; the
+    latter with src_key="rendered_phys_rgb") with goliath_amd.effnet.EffNetLoss over ONE shared network
+    (gol_mbconv_front_* where the block's shape is in effnet.DISPATCH), without importing ca_code.loss.effnet or
+    torchvision; the default (None) leaves both untouched.  With perceptual= and effnet= given, every loss of the hand
+    configs has an implementation here; every other entry of the registry stays the reference's."""
     from . import losses
 
     if registry_module is None:
@@ -582,6 +587,15 @@ def patch_losses(registry_module=None, regularizers=False, images=False, percept
         features = perceptual_module.as_features(perceptual)
         registry_module.loss_registry["vgg"] = \
             lambda assets=None, **kwargs: perceptual_module.VGGLoss(assets, features=features, **kwargs)
+    if effnet is not None:
+        from . import effnet as effnet_module
+
+        network = effnet_module.as_features(effnet)
+        registry_module.loss_registry["effnet"] = \
+            lambda assets=None, **kwargs: effnet_module.EffNetLoss(assets, features=network, **kwargs)
+        registry_module.loss_registry["effnet_phys"] = \
+            lambda assets=None, **kwargs: effnet_module.EffNetLoss(assets, features=network, src_key="rendered_phys_rgb",
+                                                                   **kwargs)
     return registry_module
 
 

@@ -659,6 +659,38 @@ int gol_conv3_bwd_x(int B, int Ci, int Co, int H, int W, int image_in, int pool,
                     const float* y, const unsigned char* pos, const float* g_y, float* g_x, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * gol_mbconv_front_fwd / gol_mbconv_front_bwd_x: the front of an MBConv block of the frozen EfficientNet-B0 feature
+ * network of the `effnet` / `effnet_phys` losses (ca_code/loss/effnet.py:45-51 runs torchvision's
+ * efficientnet_b0().features[0:4]; registered at ca_code/loss/perceptual.py:60-69): expand 1x1 + BN + SiLU, depthwise
+ * k x k / stride s + BN, and the squeeze of the squeeze-excite, as one operator.  Replaces the MIOpen 1x1 and depthwise
+ * convolutions, two batch_norm and two silu passes and the adaptive average pool; the expanded tensor never exists in
+ * memory.  BatchNorm is folded into (weight, bias) by the caller.  Expand in exact fp32 on v_mfma_f32_16x16x4_f32.
+ *   x [B,Ci,H,W]; w_e [Ce,Ci]; b_e [Ce]; w_d [Ce,k,k]; b_d [Ce]; p = (k - 1) / 2; Ho = (H + 2p - k) / stride + 1, Wo alike
+ *   e = SiLU(sum_ci w_e[c,ci] x[b,ci] + b_e[c])      (expand = 0: e = x, Ci == Ce, w_e and b_e may be NULL)
+ *   z [B,Ce,Ho,Wo] = sum_taps w_d[c,ky,kx] epad[b,c, ro stride - p + ky, co stride - p + kx] + b_d[c]   (pre-activation)
+ *   epad = e inside the image, 0 outside (NOT SiLU(b_e))
+ *   partials [B,Ce,T] (double), T = gol_mbconv_front_tiles(H, W, k, stride): per output tile the sum of SiLU(z) over the
+ *   tile, taken from the accumulators in a fixed order; ssum[b,c] = sum_t partials[b,c,t] is the caller's.
+ *   SiLU(v) = v / (1 + expf(-v)), accurate expf, IEEE division.
+ * gol_mbconv_front_bwd_x: the input gradient only (the weights are frozen).  z = the forward's z.
+ *   g_zt = g_z + g_ssum[b,c] SiLU'(z), SiLU'(v) = sg (1 + v (1 - sg)), sg = 1 / (1 + expf(-v)), formed while loading
+ *   g_e = the transposed depthwise convolution of g_zt, read from the same w_d with mirrored taps
+ *   g_x [B,Ci,H,W] written = sum_c w_e[c,ci] g_e SiLU'(e_pre), e_pre recomputed from x; expand = 0: g_x = g_e (x may be NULL)
+ *   No atomics, no scratch: bitwise reproducible.
+ * Supported: k 3 or 5; stride 1 or 2; Ci % 8 == 0; Ce % 16 == 0; Ci == Ce without expand; any H, W >= 1; B <= 65535:
+ * everything else returns GOL_ERR_UNSUPPORTED (gol_mbconv_front_tiles: 0).  A null pointer with positive sizes returns
+ * GOL_ERR_INVALID_ARG; B == 0 returns GOL_OK without a launch.  No host sync, no allocation: one launch each, capturable
+ * as a linear graph.
+ * ---------------------------------------------------------------------------------------- */
+int gol_mbconv_front_tiles(int H, int W, int k, int stride);
+int gol_mbconv_front_fwd(int B, int Ci, int Ce, int H, int W, int k, int stride, int expand, const float* x,
+                         const float* w_e, const float* b_e, const float* w_d, const float* b_d, float* z, double* partials,
+                         void* stream);
+int gol_mbconv_front_bwd_x(int B, int Ci, int Ce, int H, int W, int k, int stride, int expand, const float* x,
+                           const float* w_e, const float* b_e, const float* w_d, const float* z, const float* g_z,
+                           const float* g_ssum, float* g_x, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * SSIM image loss ("next" row).  Replaces `ssim` / `_ssim`
  * (ca_code/utils/ssim.py:25-65) as used by rgb_ssim (ca_code/loss/__init__.py:478-494): 11x11 Gaussian
  * window (sigma 1.5, zero padding), C1 = 0.01^2, C2 = 0.03^2, masked mean.
