@@ -29,116 +29,17 @@
 //             tiles; U comes from the forward's loader.  K (the 8 x 32 tiles of all views) is split over workgroups,
 //             the partial sums go to scratch and a second kernel adds them in a fixed order (bitwise reproducible).
 //     bwd_s   the streaming rest: g_bias = sum_b g_pre (mode 0), g_gb = scale g_y when the gate gradient is not wanted.
-#include "gol_common.h"
+#include "gol_upconv.h"  // the coordinate tables, up_stage_u, up_conv_core, the weight gradient's reduction
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct UpDims {
   int B, Ci, Co, Hi, Wi, H, W, mode;
   float leak, scale;
 };
 
-constexpr int kTH = 8, kTW = 32;              // output tile of the forward and of the weight gradient
-constexpr int kHR = kTH + 2, kHC = kTW + 2;   // its haloed window of U
-constexpr int kFwdKC = 8;                     // input channels per K stage of the forward
-constexpr int kFwdPlane = 400;                // >= 10 * 34, == 16 (mod 64): the 4 channel groups of a B read cover the banks
-constexpr int kBwPlane = 388;                 // >= 10 * 34, ==  4 (mod 64): 16 channels x 4 consecutive pixels cover the banks
-constexpr int kBwGRow = 260;                  // 256 pixels of g_pre per channel, == 4 (mod 64)
-
-constexpr int kSH = 4, kSW = 16;              // tile of x of the input gradient
-constexpr int kUR = 12, kUC = 36;             // the region of g_U that reaches it (see up_first_row)
-constexpr int kGR = kUR + 2, kGC = kUC + 2;   // haloed window of g_pre
-constexpr int kBxPlane = 592;                 // >= 14 * 38, == 16 (mod 64)
-constexpr int kBxNPT = 7;                     // pixel tiles of 16 per wave: 4 x 7 x 16 >= 12 x 36 = 27 x 16
-
-// ---- the coordinate rule ---------------------------------------------------------------------------------------------
-// Tables of n rows (or columns) origin .. origin + n - 1 of U: source offsets a = r0 * mul, b = r1 * mul and the fraction;
-// a = -1 marks a row outside [0, nout).
-__device__ __forceinline__ void up_fill_axis(int* s_a, int* s_b, float* s_f, int n, int origin, int nsrc, int nout, int mul,
-                                             int tid) {
-  for (int t = tid; t < n; t += 256) {
-    const int r = origin + t;
-    int a = -1, b = 0;
-    float f = 0.f;
-    if (r >= 0 && r < nout) {
-      const int nr = r * (nsrc - 1), d = nout - 1;  // (nout = 2 nsrc >= 2)
-      const int q = nr / d;
-      f = (float)(nr - q * d) / (float)d;
-      a = q * mul;
-      b = min(q + 1, nsrc - 1) * mul;
-    }
-    s_a[t] = a;
-    s_b[t] = b;
-    s_f[t] = f;
-  }
-}
-
-// first row of U with r (nsrc-1)/(nout-1) > i - 1: no earlier row reaches source row i
-__device__ __forceinline__ int up_first_row(int i, int nsrc, int nout) {
-  return (i <= 0 || nsrc <= 1) ? 0 : ((i - 1) * (nout - 1)) / (nsrc - 1) + 1;
-}
-
-// KC planes of the ROWS x COLS window of U into LDS, blended from x; outside the image and past Ci: zeros
-template <int KC, int ROWS, int COLS, int PLANE, int UNROLL>
-__device__ __forceinline__ void up_stage_u(float* s_u, const int* s_ra, const int* s_rb, const float* s_rf, const int* s_ca,
-                                           const int* s_cb, const float* s_cf, const float* __restrict__ xb, int ci0, int Ci,
-                                           size_t HWi, int tid) {
-  // an item = one window position x 4 channels: the tables and the four offsets are looked up once per item.  The loads
-  // are unconditional (clamped to texel 0 / the last channel, the value is dropped); with the loop unrolled (UNROLL = 8)
-  // a thread's loads are all in flight together, at the price of the registers that hold them (UNROLL = 1: one item's).
-  constexpr int N = (KC / 4) * ROWS * COLS;
-#pragma unroll UNROLL
-  for (int it = 0; it < (N + 255) / 256; ++it) {
-    const int idx = tid + 256 * it, idc = min(idx, N - 1);
-    const int grp = idc / (ROWS * COLS), pos = idc - grp * (ROWS * COLS), rr = pos / COLS, cc = pos - rr * COLS;
-    const int ra = s_ra[rr], ca = s_ca[cc], rb = s_rb[rr], cb = s_cb[cc];
-    const float fr = s_rf[rr], fc = s_cf[cc];
-    const bool in = ra >= 0 && ca >= 0;
-    const int o00 = in ? ra + ca : 0, o01 = in ? ra + cb : 0, o10 = in ? rb + ca : 0, o11 = in ? rb + cb : 0;
-    float x00[4], x01[4], x10[4], x11[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float* pl = xb + (size_t)min(ci0 + grp * 4 + u, Ci - 1) * HWi;
-      x00[u] = pl[o00]; x01[u] = pl[o01]; x10[u] = pl[o10]; x11[u] = pl[o11];
-    }
-    if (idx < N) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int ch = grp * 4 + u;
-        const float v = (1.f - fr) * ((1.f - fc) * x00[u] + fc * x01[u]) + fr * ((1.f - fc) * x10[u] + fc * x11[u]);
-        s_u[ch * PLANE + pos] = (in && ci0 + ch < Ci) ? v : 0.f;
-      }
-    }
-  }
-}
-
 __device__ __forceinline__ float up_gpre(const UpDims& p, float g, float aux) {
   return p.mode == 0 ? g * (aux > 0.f ? 1.f : p.leak) : p.scale * g * aux;
-}
-
-// D[m][pixel] += sum_{k, tap} A[m][k][tap] In[k][pixel + tap]: s_w[tap][k][16 CT], s_in[k][rows][cols] with plane / row
-// strides; poff = offset of the pixel's window origin
-template <int CT, int NPT, int KC>
-__device__ __forceinline__ void up_conv_core(const float* s_in, int plane, int rowstride, const float* s_w,
-                                             const int (&poff)[NPT], f32x4 (&acc)[NPT][CT], int j, int g) {
-#pragma unroll
-  for (int tap = 0; tap < 9; ++tap) {
-    const int ky = tap / 3, kx = tap - 3 * ky;
-#pragma unroll
-    for (int kk = 0; kk < KC / 4; ++kk) {
-      float a[CT];
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) a[ct] = s_w[((tap * KC + kk * 4 + g) * CT + ct) * 16 + j];
-#pragma unroll
-      for (int pt = 0; pt < NPT; ++pt) {
-        const float bv = s_in[(kk * 4 + g) * plane + poff[pt] + ky * rowstride + kx];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) acc[pt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ct], bv, acc[pt][ct], 0, 0, 0);
-      }
-    }
-  }
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
@@ -398,28 +299,6 @@ __global__ __launch_bounds__(256) void up_bwd_w_kernel(const UpDims p, const flo
   for (int tap = 0; tap < 9; ++tap) dst[tap * 256] = s_red[tap * 256 + tid];
 }
 
-// gw[co,ci,tap] = sum over the K blocks.  grid (9 taps x 16 co rows, channel tile pairs): a workgroup owns 16 outputs and
-// sums them as 16 interleaved K slices that meet in LDS in slice order -- a fixed order.
-__global__ __launch_bounds__(256) void up_bwd_w_reduce_kernel(const UpDims p, int nblk, const float* __restrict__ scratch,
-                                                              float* __restrict__ gw) {
-  __shared__ float s_part[16][16];
-  const int tap = blockIdx.x >> 4, row = blockIdx.x & 15, cl = threadIdx.x & 15, ks = threadIdx.x >> 4;
-  const int nci = (p.Ci + 15) >> 4, cot = blockIdx.y / nci, cit = blockIdx.y - cot * nci;
-  const int co = cot * 16 + row, ci = cit * 16 + cl;
-  if (co >= p.Co) return;  // block-uniform (Co <= 4)
-  const float* src = scratch + ((size_t)blockIdx.y * nblk) * (9 * 256) + tap * 256 + row * 16 + cl;
-  float acc = 0.f;
-#pragma unroll 4
-  for (int k = ks; k < nblk; k += 16) acc += src[(size_t)k * (9 * 256)];
-  s_part[ks][cl] = acc;
-  __syncthreads();
-  if (ks == 0 && ci < p.Ci) {
-#pragma unroll
-    for (int q = 1; q < 16; ++q) acc += s_part[q][cl];
-    gw[((size_t)co * p.Ci + ci) * 9 + tap] = acc;
-  }
-}
-
 // ---- streaming gradients ---------------------------------------------------------------------------------------------
 // mode 0: out[n] = sum_b g_pre[b,n] over the Co H W plane elements;  mode 1: out[n] = scale g[n] over all B Co H W
 __global__ __launch_bounds__(256) void up_bwd_s_kernel(const UpDims p, size_t N, const float* __restrict__ paux,
@@ -454,10 +333,7 @@ int check_common(int B, int Ci, int Co, int Hi, int Wi, int mode, float leak) {
 int bwd_w_groups(int Ci, int Co) { return gol_cdiv(Co, 16) * gol_cdiv(Ci, 16); }
 
 int bwd_w_blocks(int B, int Ci, int Co, int Hi, int Wi) {
-  const long long ntiles = (long long)B * gol_cdiv(2 * Hi, kTH) * gol_cdiv(2 * Wi, kTW), pairs = bwd_w_groups(Ci, Co);
-  long long nblk = (768 + pairs - 1) / pairs;  // one round of the resident workgroups: 3 per CU (LDS) on 256 CUs
-  nblk = nblk > ntiles ? ntiles : nblk;
-  return (int)(nblk < 1 ? 1 : nblk);
+  return up_bwd_w_blocks((long long)B * gol_cdiv(2 * Hi, kTH) * gol_cdiv(2 * Wi, kTW), bwd_w_groups(Ci, Co));
 }
 
 template <int EPI>
@@ -522,7 +398,7 @@ extern "C" int gol_upconv_bwd(int B, int Ci, int Co, int Hi, int Wi, int mode, f
     const int groups = bwd_w_groups(Ci, Co), nblk = bwd_w_blocks(B, Ci, Co, Hi, Wi);
     up_bwd_w_kernel<<<dim3(nblk, groups), 256, 0, s>>>(p, x, aux, g_y, scratch);
     GOL_CHECK_LAUNCH();
-    up_bwd_w_reduce_kernel<<<dim3(9 * 16, groups), 256, 0, s>>>(p, nblk, scratch, g_w);
+    up_bwd_w_reduce_kernel<<<dim3(9 * 16, groups), 256, 0, s>>>(Co, Ci, Ci, gol_cdiv(Ci, 16), gol_cdiv(Ci, 16), nblk, scratch, g_w);
     GOL_CHECK_LAUNCH();
   }
   if (g_bias) {

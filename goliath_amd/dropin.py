@@ -622,7 +622,8 @@ def patch_image_ops(*modules):
     return done
 
 
-def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, texture_decoder=False, texture_tail=False):
+def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, texture_decoder=False, texture_tail=False,
+                 displacement_unet=False):
     """BASELINE config 4 as a drop-in: `ConvTeacherDecoder.forward` (ca_code/models/urhand.py:349-630) with its two light
     loops and both shadow-map evaluations on the HIP kernels (goliath_amd.urhand.conv_teacher_decoder_forward) and the
     stand-alone shadow-map lookup (`get_shadow_map`, imported at urhand.py:44).  The depth images of the light cameras are
@@ -661,8 +662,18 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, t
     a deterministic seam backward).  The seam tap list is packed on first use from `seam_sampler.uvs` / `.weights` and
     cached on the sampler.  Opt-in: the default leaves `AutoEncoder.forward` untouched (and puts the original back after
     an earlier texture_tail=True).  Measured by tools/uvtex_probe.py (profiles/uvtex_probe.json, DESIGN.md section 8
-    "uvtex").  Returns the patched module."""
-    from . import meshraster, shadowmap, texdec, urhand, uvtex
+    "uvtex").
+
+    displacement_unet=True sets `dispunet.DISPLACEMENT_UNET_FLAG` on the decoder class: either forward then runs its
+    displacement / roughness UNet (`self.geo_refiner`, urhand.py:461; DisplacementUNet.forward, :200-242) through
+    goliath_amd.dispunet.forward, provided the refiner has `enc_layers`, `dec_layers` and `dec_layers_roughness` (any other
+    refiner is called as a module, as today).  A decoder level -- LeakyReLU + exact 2x bilinear resize + concat with the
+    skip + weight-normalised 3x3 convolution + untied bias, tanh and affine at the last level -- goes to the fused operator
+    (gol_upcat_conv_fwd / _bwd: neither the upsampled nor the concatenated tensor exists in memory) where its shape is in
+    dispunet.DISPATCH, and runs the reference's lines everywhere else.  Opt-in: the default binding clears the flag and is
+    unchanged.  Measured per level and for the whole UNet by tools/dispunet_probe.py (profiles/dispunet_probe.json,
+    DESIGN.md section 6c-bis).  Returns the patched module."""
+    from . import dispunet, meshraster, shadowmap, texdec, urhand, uvtex
 
     if urhand_module is None:
         import ca_code.models.urhand as urhand_module
@@ -687,6 +698,7 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, t
     urhand_module.ConvTeacherDecoder.forward = (urhand.conv_teacher_decoder_forward_uv_frames if uv_frames
                                                 else urhand.conv_teacher_decoder_forward)
     setattr(urhand_module.ConvTeacherDecoder, texdec.TEXTURE_DECODER_FLAG, bool(texture_decoder))
+    setattr(urhand_module.ConvTeacherDecoder, dispunet.DISPLACEMENT_UNET_FLAG, bool(displacement_unet))
     ae = urhand_module.AutoEncoder if texture_tail else getattr(urhand_module, "AutoEncoder", None)
     if texture_tail:
         if "_gol_reference_forward" not in ae.__dict__:

@@ -14,6 +14,9 @@
     either forward, where the decoder class carries texdec.TEXTURE_DECODER_FLAG (dropin.patch_urhand(texture_decoder=True)):
         * the two 7-layer texture branches (:583-608): 2x bilinear resize + weight-normalised 3x3 conv + bias / LeakyReLU
           or gate / gainbias per layer               -> gol_upconv_fwd/bwd (goliath_amd.texdec), per shape, opt-in
+    either forward, where the decoder class carries dispunet.DISPLACEMENT_UNET_FLAG (dropin.patch_urhand(displacement_unet=True)):
+        * the decoder levels of the displacement / roughness UNet (:217-226, :231-239): leaky + 2x bilinear resize + concat +
+          weight-normalised 3x3 conv (+ tanh head)     -> gol_upcat_conv_fwd/bwd (goliath_amd.dispunet), per shape, opt-in
     olat_rgb_decoder_forward_rgb   <- /root/reference/ca_code/models/hand_teacher_mvp.py:253-494
         * the deep-shadow march (:271-358: L-fold copies of the primitive set and of a 4-channel template, an ordinary
           ray march with with_shadow=True) -> gol_mvp_shadow_march (all lights of a frame share transforms, tree and an
@@ -43,7 +46,7 @@ from typing import List, Optional
 import torch
 import torch.nn.functional as F
 
-from . import _lib, meshraster, mvp, mvpprims, olat, shadowmap, texdec, uvframes, uvlight, uvtex
+from . import _lib, dispunet, meshraster, mvp, mvpprims, olat, shadowmap, texdec, uvframes, uvlight, uvtex
 from .imgtail import cal_v5_matrix
 
 
@@ -185,7 +188,11 @@ def _decoder_forward(self, fused_frames, lbs_motion, id_mesh, tex_mean, verts_re
         refiner_in = torch.cat([uv_id_mesh, nml], dim=1)
     else:
         raise NotImplementedError("{} not supported".format(self.feat_uv))
-    displacement, roughness, id_pose_feat = self.geo_refiner(refiner_in, pose_cond)
+    if (getattr(type(self), dispunet.DISPLACEMENT_UNET_FLAG, False)       # dropin.patch_urhand(displacement_unet=True)
+            and all(hasattr(self.geo_refiner, a) for a in ("enc_layers", "dec_layers", "dec_layers_roughness"))):
+        displacement, roughness, id_pose_feat = dispunet.forward(self.geo_refiner, refiner_in, pose_cond)
+    else:
+        displacement, roughness, id_pose_feat = self.geo_refiner(refiner_in, pose_cond)
     if not self.refine_geo:
         displacement = displacement * 0
     p_uv = p_uv + nml.detach() * displacement

@@ -625,6 +625,48 @@ int gol_upconv_bwd(int B, int Ci, int Co, int Hi, int Wi, int mode, float leak, 
                    float* g_bias, float* g_gate, float* g_gb, float* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Decoder level of URHand's DisplacementUNet as one operator: LeakyReLU of the previous layer's output + exact 2x
+ * bilinear resize (align_corners=True) + concat with the encoder's skip + weight-normalised 3x3 / stride 1 / pad 1
+ * convolution + untied bias (+ tanh and an affine at the last level).  Replaces, per level 1..n of the two decoder branches of
+ * DisplacementUNet.forward (ca_code/models/urhand.py:217-226 and :231-239; layers built at :164-193 from
+ * la.Conv2dWNUB(.., 3, 1, 1), ca_code/nn/layers.py:276-328),
+ *   F.leaky_relu(x, 0.2), F.interpolate(x, size=x_prev.shape[2:4], mode="bilinear", align_corners=True),
+ *   th.cat([x, x_prev], 1), the MIOpen convolution, the ATen add of the untied bias and, after the last level, tanh and
+ *   x * output_scale (:227-228) or (x + 1) / 4 + 0.3 (:240-241):
+ *   L             = xa > 0 ? xa : leak * xa          (the adjoint at xa == 0 takes leak, as torch)
+ *   U             = bilinear 2x of L by the integer-ratio rule of gol_upconv_* above (H = 2 Hi, W = 2 Wi)
+ *   X             = concat(U, xb) over channels: U is channels 0..Ca-1 of the weight, xb is channels Ca..Ca+Cb-1
+ *   acc[b,co,r,c] = sum_{k,ky,kx} Xpad[b,k,r-1+ky,c-1+kx] w_eff[co,k,ky,kx]            (Xpad = X inside the image, 0 outside)
+ *   act 0:  y = acc + bias[co,r,c]                   (the next level applies the leaky itself)
+ *   act 1:  y = tanh(acc + bias[co,r,c]) * out_scale + out_shift
+ *           (displacement: out_scale = output_scale, out_shift = 0; roughness: out_scale = 0.25, out_shift = 0.55)
+ *   xa [B,Ca,Hi,Wi] (the previous layer's output BEFORE its activation); xb [B,Cb,H,W]; w_eff [Co,Ca+Cb,3,3] (the weight
+ *   norm already applied, goliath_amd/tail.py:wn_weight); bias [Co,H,W]; y [B,Co,H,W].  fp32 MFMA, exact fp32.  L, U and X
+ *   never exist in memory; nothing but y is written.
+ * Ca and Cb must be positive multiples of 8 and Co a multiple of 8 or one of 1..4 (zero weight rows), B <= 65535, any
+ * Hi, Wi >= 1; otherwise GOL_ERR_UNSUPPORTED.  A null pointer with positive sizes is GOL_ERR_INVALID_ARG; B == 0 is GOL_OK
+ * without a launch.
+ * bwd forms g_pre = g_y (act 0) or g_y * out_scale * (1 - t^2) with t = (y - out_shift) / out_scale recovered from y
+ * (act 1; needs y) while loading; any of the outputs may be NULL = not wanted, at no cost:
+ *   g_xa [B,Ca,Hi,Wi] written: the bilinear adjoint of the transposed convolution of g_pre over channels 0..Ca-1, gathered
+ *       per source texel from a region of g_U kept on chip (no atomics), times the leaky mask of xa; needs xa and w_eff;
+ *   g_xb [B,Cb,H,W] written: the transposed convolution of g_pre over channels Ca.. (mirrored taps, no flipped copy of
+ *       the weight); needs w_eff;
+ *   g_w [Co,Ca+Cb,3,3] written (= sum_{b,r,c} g_pre Xpad, U recomputed from xa); needs xa, xb and
+ *       scratch[gol_upcat_conv_bwd_scratch_floats] (per-workgroup partial sums added in a fixed order by a second kernel:
+ *       no float atomics, bitwise reproducible);
+ *   g_bias [Co,H,W] written (= sum_b g_pre).
+ * No host sync, no allocation: both calls can be captured as a linear graph.
+ * ---------------------------------------------------------------------------------------- */
+int gol_upcat_conv_fwd(int B, int Ca, int Cb, int Co, int Hi, int Wi, int act, float leak, float out_scale,
+                       float out_shift, const float* xa, const float* xb, const float* w_eff, const float* bias, float* y,
+                       void* stream);
+long long gol_upcat_conv_bwd_scratch_floats(int B, int Ca, int Cb, int Co, int Hi, int Wi);
+int gol_upcat_conv_bwd(int B, int Ca, int Cb, int Co, int Hi, int Wi, int act, float leak, float out_scale,
+                       float out_shift, const float* xa, const float* xb, const float* w_eff, const float* y,
+                       const float* g_y, float* g_xa, float* g_xb, float* g_w, float* g_bias, float* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * gol_conv3_fwd / gol_conv3_bwd_x: a layer of the frozen VGG19 feature network of the masked perceptual loss
  * (ca_code/loss/vgg.py:17-88; `vgg`, ca_code/loss/perceptual.py:55-58) as one operator: 3x3 / stride 1 / zero padding 1
  * convolution + bias + ReLU, optionally on the normalised image and optionally followed by the 2x2 max-pool.  Replaces
