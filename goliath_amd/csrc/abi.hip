@@ -39,3 +39,16 @@ extern "C" int gol_selftest_wave_sum8(const float* in512, float* out64, void* st
   GOL_CHECK_LAUNCH();
   return GOL_OK;
 }
+
+// in384: six rows of 64 lane values (s0, s1, s2, m0, my, myy); dx64: the factor of every lane (equal in lanes l and l + 16);
+// out64[l] = what gol_wave_colsum returns in lane l (tests/test_gpu_wave_colsum.py)
+__global__ void selftest_wave_colsum_kernel(const float* __restrict__ in, const float* __restrict__ dx,
+                                            float* __restrict__ out) {
+  const int l = threadIdx.x;
+  out[l] = gol_wave_colsum(in[l], in[64 + l], in[128 + l], in[192 + l], in[256 + l], in[320 + l], dx[l]);
+}
+extern "C" int gol_selftest_wave_colsum(const float* in384, const float* dx64, float* out64, void* stream) {
+  selftest_wave_colsum_kernel<<<1, 64, 0, (hipStream_t)stream>>>(in384, dx64, out64);
+  GOL_CHECK_LAUNCH();
+  return GOL_OK;
+}

@@ -129,6 +129,50 @@ __device__ __forceinline__ float gol_wave_sum8(float a0, float a1, float a2, flo
   return r;
 }
 
+// Nine wave-wide sums of a 4 x 16 lane grid (lane = 16 r + x) in 20 instructions, when three of them are x-moments of two
+// of the others: from a lane's six partial sums (s0, s1, s2, m0, my, myy) and a factor dx that depends on the column x only,
+//   sum(s0), sum(s1), sum(s2), sum(myy), M0 = sum(m0), My = sum(my), Mx = sum(dx m0), Mxx = sum(dx^2 m0), Mxy = sum(dx my).
+// With C0(x) and C1(x) the column sums of m0 and my over the four rows, Mx = sum_x dx C0, Mxx = sum_x dx^2 C0 and Mxy =
+// sum_x dx C1: only six values cross the rows, and the products are formed on column sums, not per lane ahead of the fold.
+//   1. cross-row: two 4-way folds of the six values.  P gets the column sums of (s0, s2, s1, myy), one per row; the fold
+//      of (m0, my) swapped with its own copy leaves Q with rows (C0, C0, C1, C1).
+//   2. on column sums: rows 1 and 3 of Q times dx (a row-masked DPP multiply, the other rows keep their value): rows
+//      (C0, dx C0, C1, dx C1); U = Q dx has dx^2 C0 in row 1 (its other rows are not used).
+//   3. in-row: X + row_ror:8(X) holds a row's 8 pair sums in both halves (gol_wave_sum8); the halves of P and Q are folded
+//      once more with row_ror:4 into banks 1 and 3 (lanes 4-7: the quad sums of P, lanes 12-15: those of Q), the quad sums
+//      of U go into bank 0, and row_shr 1 and 2 add the four quad sums of each bank up.
+// Results, lane 16 r + c of the returned register:
+//   lane      3     7    15    19    23    31    35    39    47    51    55    63
+//   sum      (Mx)   s0   M0    Mxx   s2    Mx    -     s1    My    -     myy   Mxy          (lanes 16 r + 11: not a sum)
+// Precondition: dx is the same in lanes l and l + 16 (a function of l & 15); lanes that break it get sums of no meaning.
+// Stages 2 and 3 are one block of assembly (no builtin multiplies or adds into part of a register, and the compiler would
+// sink what only the result lanes consume into their branch): a DPP read needs two wait states after a VALU write of its
+// source, and inside the block the steps of P, Q and U are interleaved so that they fill most of each other's.
+__device__ __forceinline__ float gol_wave_colsum(float s0, float s1, float s2, float m0, float my, float myy, float dx) {
+  const float a01 = gol_swap32_sum(s0, s1), a2y = gol_swap32_sum(s2, myy);
+  const float c = gol_swap32_sum(m0, my);   // rows 0, 1: halves of C0; rows 2, 3: halves of C1
+  float p = gol_swap16_sum(a01, a2y);       // rows: s0, s2, s1, myy
+  float q = gol_swap16_sum(c, c);           // rows: C0, C0, C1, C1
+  float u;
+  asm("s_nop 1\n\t"
+      "v_mul_f32_dpp %1, %1, %3 quad_perm:[0,1,2,3] row_mask:0xa bank_mask:0xf\n\t"   // rows 1, 3: dx C0, dx C1
+      "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"             // pair sums of P
+      "v_mul_f32_e32 %2, %1, %3\n\t"                                                  // row 1: dx^2 C0
+      "v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"             // lanes 8-15: pair sums of Q
+      "s_nop 0\n\t"
+      "v_add_f32_dpp %2, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"             // pair sums of U
+      "v_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"             // banks 1, 3: quad sums of P, Q
+      "s_nop 0\n\t"
+      "v_add_f32_dpp %0, %2, %2 row_ror:4 row_mask:0xf bank_mask:0x1\n\t"             // bank 0: quad sums of U
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+      : "+v"(p), "+v"(q), "=&v"(u)
+      : "v"(dx));
+  return p;
+}
+
 // element at a 32-bit BYTE offset from a (wave-uniform) base pointer: the SGPR-base + VGPR-offset addressing form
 // (64-bit per-lane address arithmetic costs several quarter-rate vector instructions per access)
 template <typename T>

@@ -228,34 +228,40 @@ __device__ __forceinline__ void fwd_take(const bool (&take)[PPL], const fvec<PPL
 #endif
 }
 
-// Backward: capped alpha and the lane masks mv[] of the pixels that took entry li (within the pixel's list && !(sigma < 0
-// || alpha < 1/255): ballots of the plain compares, the ballot of a combined bool costs a v_cndmask + v_cmp); returns their union
+// Backward: raw = opacity e, the uncapped alpha, and the lane masks mv[] of the pixels that took entry li (within the pixel's
+// list && !(sigma < 0 || alpha < 1/255): ballots of the plain compares, the ballot of a combined bool costs a v_cndmask +
+// v_cmp); returns their union.  The alpha of the test is min(cap, raw); the compare is made on raw itself, which decides the
+// same for every input: the cap lies above 1/255, so min(cap, raw) < 1/255 exactly when raw < 1/255, and a NaN raw (v_min
+// returns the cap for it) is "not below" either way.
 template <int PPL>
 __device__ __forceinline__ unsigned long long bwd_taken(float opacity, const fvec<PPL>& e, const fvec<PPL>& sigma, int li,
-                                                        const ivec<PPL>& bin_final, fvec<PPL>& alpha,
+                                                        const ivec<PPL>& bin_final, fvec<PPL>& raw,
                                                         unsigned long long (&mv)[PPL]) {
-  alpha = opacity * e;
+  static_assert(GOL_ALPHA_CAP_BWD > GOL_ALPHA_FLOOR, "bwd_taken tests the uncapped alpha against the floor");
+  raw = opacity * e;
   unsigned long long many = 0ull;
 #pragma unroll
   for (int q = 0; q < PPL; ++q) {
-    alpha[q] = fminf(GOL_ALPHA_CAP_BWD, alpha[q]);
-    mv[q] = gol_ballot(li <= bin_final[q]) & gol_ballot(!(sigma[q] < 0.f)) & gol_ballot(!(alpha[q] < GOL_ALPHA_FLOOR));
+    mv[q] = gol_ballot(li <= bin_final[q]) & gol_ballot(!(sigma[q] < 0.f)) & gol_ballot(!(raw[q] < GOL_ALPHA_FLOOR));
     many |= mv[q];
   }
   return many;
 }
 
 // Backward: T steps back over the entry (T_cur becomes the transmittance in front of it); ra = 1 / (1 - alpha),
-// fac = alpha T = the entry's compositing weight
+// fac = alpha T = the entry's compositing weight.  The ONE mask of a visit is applied here, to raw: it leaves as raw_m.
 template <int PPL>
-__device__ __forceinline__ void bwd_recur(const unsigned long long (&mv)[PPL], fvec<PPL>& alpha, fvec<PPL>& T_cur,
-                                          bool (&v)[PPL], fvec<PPL>& ra, fvec<PPL>& fac) {
+__device__ __forceinline__ void bwd_recur(const unsigned long long (&mv)[PPL], fvec<PPL>& raw, fvec<PPL>& T_cur,
+                                          fvec<PPL>& alpha, fvec<PPL>& ra, fvec<PPL>& fac) {
 #pragma unroll
   for (int q = 0; q < PPL; ++q) {
-    v[q] = __builtin_amdgcn_inverse_ballot_w64(mv[q]);
-    // an entry the pixel did not take enters with alpha = 0: 1 / (1 - 0) = 1 exactly, so T and the running sums pass
-    // through unchanged without further selects (the composite R of bwd_moments likewise)
-    alpha[q] = v[q] ? alpha[q] : 0.f;
+    // an entry the pixel did not take enters with raw_m = 0 and so with alpha = 0: 1 / (1 - 0) = 1 exactly, so T and the
+    // running sums pass through unchanged without further selects (the composite R of bwd_moments likewise), and its gop,
+    // a multiple of raw_m, is 0 as well
+    raw[q] = __builtin_amdgcn_inverse_ballot_w64(mv[q]) ? raw[q] : 0.f;
+    // min(cap, raw_m), written as the instruction: fminf on the result of a select is compiled to v_max x, x (a
+    // canonicalisation that the product under the select does not need) + v_min, and v_med3 wants the cap in a register
+    asm("v_min_f32_e32 %0, %2, %1" : "=v"(alpha[q]) : "v"(raw[q]), "i"(__builtin_bit_cast(int, GOL_ALPHA_CAP_BWD)));
   }
   const fvec<PPL> one_m = 1.f - alpha;
 #pragma unroll
@@ -265,7 +271,7 @@ __device__ __forceinline__ void bwd_recur(const unsigned long long (&mv)[PPL], f
   T_cur = T_new;
 }
 
-// Backward: v_alpha and gop = e v_alpha with its first two moments in dy, per pixel (lane_sum adds a lane's pixels up).
+// Backward: v_alpha and gop = raw_m v_alpha with its first two moments in dy, per pixel (lane_sum adds a lane's pixels up).
 // gsplat: v_alpha = sum_c (rgb_c T - buffer_c ra) v_out_c + T_final ra (v_out_alpha - <bg, v_out>) with buffer_c = sum over
 // the Gaussians behind of rgb_c alpha T.  All channels enter through ONE dot product with the upstream gradient, w =
 // <colour, v_out>, so the colour buffers collapse into a running scalar q = sum_behind fac w and v_alpha = T w - ra (q - tail),
@@ -275,18 +281,17 @@ __device__ __forceinline__ void bwd_recur(const unsigned long long (&mv)[PPL], f
 //   v_alpha = T (w - R),   R <- R (1 - alpha) + alpha w = R + alpha (w - R),   R_start = <bg, v_out> - v_out_alpha
 // -- one running quantity, no T_final factor, no division, and no difference of two sums scaled up by ra when alpha is
 // near its cap.  An entry the pixel did not take has alpha = 0 (bwd_recur) and leaves R as it is.
-// d loss / d sigma per pixel is -opacity * gop; the (wave-uniform) factor -opacity is applied once per Gaussian in
-// the merge step: the lanes reduce the moments of gop itself, whose zeroth moment IS v_opacity
+// d loss / d sigma per pixel is -opacity e v_alpha = -gop: gop carries the (wave-uniform) opacity already, because the
+// masked quantity is raw_m = opacity e (0 for a pixel that did not take the entry: no select here).  The lanes reduce the
+// moments of gop; the merges negate them, and the zeroth moment is opacity * v_opacity (divided once per entry there)
 template <int PPL>
-__device__ __forceinline__ void bwd_moments(const fvec<PPL>& e, const fvec<PPL>& w, const fvec<PPL>& T_cur,
-                                            const fvec<PPL>& alpha, const bool (&v)[PPL], const fvec<PPL>& dy,
+__device__ __forceinline__ void bwd_moments(const fvec<PPL>& raw_m, const fvec<PPL>& w, const fvec<PPL>& T_cur,
+                                            const fvec<PPL>& alpha, const fvec<PPL>& dy,
                                             fvec<PPL>& R, fvec<PPL>& gop, fvec<PPL>& gy, fvec<PPL>& gyy) {
   const fvec<PPL> d = w - R;
   const fvec<PPL> v_alpha = T_cur * d;
   R += alpha * d;
-  gop = e * v_alpha;
-#pragma unroll
-  for (int q = 0; q < PPL; ++q) gop[q] = v[q] ? gop[q] : 0.f;
+  gop = raw_m * v_alpha;
   gy = gop * dy;
   gyy = gy * dy;
 }

@@ -391,7 +391,7 @@ __global__ __launch_bounds__(1024) void l1_sum_kernel(int n, const float* __rest
 }
 
 constexpr int kBatchB = 64;   // backward batch (smaller: per-wave gradient slots live in LDS)
-constexpr int kAcc = 12;      // r g b v_opacity | Mx My Mxx Mxy | Myy extra - -   (M = moments of gop, see the loop)
+constexpr int kAcc = 12;      // r g b M0 | Mx My Mxx Mxy | Myy extra - -   (M = moments of gop, M0 = opacity * v_opacity; see the loop)
 
 // ---- backward ------------------------------------------------------------------------------------
 // Same workgroup / wave / lane layout as the forward (Pix).  With two pixels per lane the per-pixel recurrences of the
@@ -488,7 +488,14 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
   bmax = min(bmax, range.y - 1);
   if (bmax < range.x) return;
 
-  float* acc_lane = &s_acc[wave][0][lane >> 3];  // this lane's column (lane 8 k + 7 holds sum k of the first eight)
+  // this lane's column of the slot rows.  PPL = 1: lane 8 k + 7 holds sum k of the first eight (gol_wave_sum8).  PPL = 2:
+  // the lanes 8 k + 7 and lane 19 hold the nine sums of gol_wave_colsum, in the slot order kColSlot (a nibble per k):
+  //   lane   7  15  23  31  39  47  55  63 | 19
+  //   slot   0   3   2   4   1   5   8   7 |  6
+  constexpr unsigned kColSlot = 0x78514230u;
+  const bool res_lane = (lane & 7) == 7 || (PPL == 2 && lane == 19);
+  const int acc_col = PPL == 1 ? lane >> 3 : lane == 19 ? 6 : (int)((kColSlot >> (4 * (lane >> 3))) & 15u);
+  float* acc_lane = &s_acc[wave][0][acc_col];
   const int n_batches = (bmax - range.x + kBatchB) / kBatchB;
   // A batch is staged through two dependent loads (list id -> the Gaussian's record).  The id of the NEXT batch's entry is
   // fetched while this batch is being worked on, so that only the record gather is left behind the barrier (nothing hides it
@@ -542,17 +549,16 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
       const int li = batch_end - t;
       const float dx = a4.x - px;
       const fv dy = a4.y - py;
-      fv sigma, vis, alpha, ra, fac;
+      fv sigma, vis, raw, alpha, ra, fac;
       visit_falloff<PPL>(a4.z, a4.w, b4.x, dx, dy, sigma, vis);
       unsigned long long mv[PPL];
-      if (bwd_taken<PPL>(b4.y, vis, sigma, li, bin_final, alpha, mv) == 0ull) continue;
-      bool v[PPL];
-      bwd_recur<PPL>(mv, alpha, T_cur, v, ra, fac);
+      if (bwd_taken<PPL>(b4.y, vis, sigma, li, bin_final, raw, mv) == 0ull) continue;
+      bwd_recur<PPL>(mv, raw, T_cur, alpha, ra, fac);
       // all channels enter through ONE dot product with the upstream gradient (see bwd_moments)
       fv w = b4.z * vo0 + b4.w * vo1 + c2.x * vo2;
       if (EXTRA) w += c2.y * vo3;
       fv gop, gy, gyy;
-      bwd_moments<PPL>(vis, w, T_cur, alpha, v, dy, R, gop, gy, gyy);
+      bwd_moments<PPL>(raw, w, T_cur, alpha, dy, R, gop, gy, gyy);
       // the colour sums of the lane's pixels (PPL = 2: one multiply + one scalar FMA per colour sum -- written on scalars:
       // from the 2-vector form the compiler builds v_mul + v_pk_fma and throws the packed op's upper half away)
       float g0s, g1s, g2s, g3 = 0.f;
@@ -566,18 +572,35 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
         if (EXTRA) g3 = fac[0] * vo3[0];
       }
       const float m0 = lane_sum<PPL>(gop), my = lane_sum<PPL>(gy), myy = lane_sum<PPL>(gyy);
-      const float mx = m0 * dx, mxx = mx * dx, mxy = my * dx;
-      // the first eight sums in one 8-way reduction: lane 16 r + 7 gets argument r, lane 16 r + 15 argument 4 + r, so with
-      // the even slots first and the odd ones after them lane 8 k + 7 holds slot k
-      const float r0 = gol_wave_sum8(g0s, g2s, mx, mxx, g1s, m0, my, mxy);
-      // the 9th (and 10th) sum: a 6-instruction DPP ladder each (total in lane 63) instead of a second 4-way reduction
-      const float r2 = gol_wave_sum_to_lane63(myy);
-      const float r3 = EXTRA ? gol_wave_sum_to_lane63(g3) : 0.f;
-      if ((lane & 7) == 7) {
-        // slot row t of this wave + a 32-bit byte offset (plain pointer arithmetic on the int t becomes a v_mad_u64_u32)
-        float* a = gol_at(acc_lane, (unsigned)t * (unsigned)(kAcc * sizeof(float)));
-        a[0] = r0;
-        if (lane == 63) { a[8 - 7] = r2; a[9 - 7] = r3; }  // (lane 63's base points at slot 7)
+      if constexpr (PPL == 2) {
+        // dx is constant down a column of lanes (lane = 16 r + x): only the six plain sums cross the rows, the three
+        // x-moments are formed on the column sums of m0 and my (gol_wave_colsum); nine results, one slot write per lane
+        // the depth gradient's sum keeps its 6-instruction DPP ladder (total in lane 63)
+        const float r3 = EXTRA ? gol_wave_sum_to_lane63(g3) : 0.f;
+        const float r0 = gol_wave_colsum(g0s, g1s, g2s, m0, my, myy, dx);
+        if (res_lane) {
+          // slot row t of this wave + a 32-bit byte offset (plain pointer arithmetic on the int t becomes a v_mad_u64_u32,
+          // and so does the offset's own multiply when one store is all that uses it: kept in an SGPR, it is one v_add_u32)
+          unsigned row_t = (unsigned)t * (unsigned)(kAcc * sizeof(float));
+          asm("" : "+s"(row_t));
+          float* a = gol_at(acc_lane, row_t);
+          a[0] = r0;
+          if (EXTRA && lane == 63) a[9 - 7] = r3;   // (lane 63's base points at slot 7; without EXTRA no merge uses slot 9)
+        }
+      } else {
+        const float mx = m0 * dx, mxx = mx * dx, mxy = my * dx;
+        // the first eight sums in one 8-way reduction: lane 16 r + 7 gets argument r, lane 16 r + 15 argument 4 + r, so with
+        // the even slots first and the odd ones after them lane 8 k + 7 holds slot k
+        const float r0 = gol_wave_sum8(g0s, g2s, mx, mxx, g1s, m0, my, mxy);
+        // the 9th (and 10th) sum: a 6-instruction DPP ladder each (total in lane 63) instead of a second 4-way reduction
+        const float r2 = gol_wave_sum_to_lane63(myy);
+        const float r3 = EXTRA ? gol_wave_sum_to_lane63(g3) : 0.f;
+        if (res_lane) {
+          // slot row t of this wave + a 32-bit byte offset (plain pointer arithmetic on the int t becomes a v_mad_u64_u32)
+          float* a = gol_at(acc_lane, (unsigned)t * (unsigned)(kAcc * sizeof(float)));
+          a[0] = r0;
+          if (lane == 63) { a[8 - 7] = r2; a[9 - 7] = r3; }  // (lane 63's base points at slot 7)
+        }
       }
       touched |= 1ull << t;
     }
@@ -614,15 +637,17 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
         }
         if (any) {
           // (the three merges keep their own arithmetic form of the weights: a common one changes these kernels' code)
-          // slots 4..8 hold moments of gop: v_sigma-sums = -opacity * moment (conic back from its log2e scaling with ln 2)
+          // slots 3..8 hold moments of gop = opacity e v_alpha (bwd_moments): v_sigma-sums = -moment (conic back from its
+          // log2e scaling with ln 2), v_opacity = M0 / opacity -- a true division, once per entry; a touched entry was taken
+          // with opacity e >= 1/255, so opacity > 0
           const float4 a4 = s_e[tid].a;
           const float4 b4 = s_e[tid].b;
-          const float nop = -b4.y, cc = b4.x;
-          const float wxx = nop * a4.z * kUnA, wxy = nop * a4.w * kUnB, wyy = nop * cc * kUnA, hnop = 0.5f * nop;
+          const float cc = b4.x;
+          const float wxx = -a4.z * kUnA, wxy = -a4.w * kUnB, wyy = -cc * kUnA;
           float4* o = reinterpret_cast<float4*>(&s_acc[0][tid][0]);
-          o[0] = make_float4(s[0], s[1], s[2], s[3]);
-          o[1] = make_float4(wxx * s[4] + wxy * s[5], wxy * s[4] + wyy * s[5], hnop * s[6], nop * s[7]);
-          *reinterpret_cast<float2*>(o + 2) = make_float2(hnop * s[8], s[9]);
+          o[0] = make_float4(s[0], s[1], s[2], s[3] / b4.y);
+          o[1] = make_float4(wxx * s[4] + wxy * s[5], wxy * s[4] + wyy * s[5], -0.5f * s[6], -s[7]);
+          *reinterpret_cast<float2*>(o + 2) = make_float2(-0.5f * s[8], s[9]);
           s_touched[0][tid] = 1;
         }
       }
@@ -678,15 +703,15 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_bwd_kernel(
         const size_t g = goff + (size_t)s_id[tid];
         const float4 a4 = s_e[tid].a;
         const float4 b4 = s_e[tid].b;
-        const float nop = -b4.y;  // slots 4..8 are moments of gop: v_sigma-sums = -opacity * moment
-        // (the packed merge's weights with -opacity factored out of the x / y sums: one thread forms all of them)
+        // slots 3..8 are moments of gop = opacity e v_alpha: v_sigma-sums = -moment, v_opacity = M0 / opacity (> 0: see
+        // the packed merge, whose weights these are with the sign factored out of the x / y sums)
         const float3 cn = true_conic(a4.z, a4.w, b4.x);
         atomicAdd(v_colors + 3 * g, a[0]); atomicAdd(v_colors + 3 * g + 1, a[1]); atomicAdd(v_colors + 3 * g + 2, a[2]);
-        atomicAdd(v_opacity + g, a[3]);
-        atomicAdd(v_xy + 2 * g, nop * (cn.x * a[4] + cn.y * a[5]));
-        atomicAdd(v_xy + 2 * g + 1, nop * (cn.y * a[4] + cn.z * a[5]));
-        atomicAdd(v_conic + 3 * g, 0.5f * nop * a[6]); atomicAdd(v_conic + 3 * g + 1, nop * a[7]);
-        atomicAdd(v_conic + 3 * g + 2, 0.5f * nop * a[8]);
+        atomicAdd(v_opacity + g, a[3] / b4.y);
+        atomicAdd(v_xy + 2 * g, -(cn.x * a[4] + cn.y * a[5]));
+        atomicAdd(v_xy + 2 * g + 1, -(cn.y * a[4] + cn.z * a[5]));
+        atomicAdd(v_conic + 3 * g, -0.5f * a[6]); atomicAdd(v_conic + 3 * g + 1, -a[7]);
+        atomicAdd(v_conic + 3 * g + 2, -0.5f * a[8]);
         if (EXTRA && v_extra) atomicAdd(v_extra + g, a[9]);
       }
     }

@@ -151,8 +151,8 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_fwd_kernel(
 }
 
 // Backward.  Same workgroup / wave / lane layout and batch walk as raster_bwd_kernel (dense gradient arrays), on CK
-// channels.  Per-visit wave sums: the CK colour sums  sum_pix fac v_out_c  and the moments of gop = vis v_alpha
-// (m0 = v_opacity, mx, my, mxx, mxy, myy; see raster_bwd_kernel), NS = CK + 6 of them, reduced four at a time.
+// channels.  Per-visit wave sums: the CK colour sums  sum_pix fac v_out_c  and the moments of gop = opacity vis v_alpha
+// (m0 = opacity * v_opacity, mx, my, mxx, mxy, myy; see raster_bwd_kernel), NS = CK + 6 of them, reduced four at a time.
 template <int CK, int PPL>
 __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
     int N, int C, int c_first, int img_h, int img_w, int tiles_x, int tiles_y, const int2* __restrict__ tile_bins,
@@ -260,19 +260,18 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
       const int li = batch_end - t;
       const float dx = a4.x - px;
       const fv dy = a4.y - py;
-      fv sigma, vis, alpha, ra, fac;
+      fv sigma, vis, raw, alpha, ra, fac;
       visit_falloff<PPL>(a4.z, a4.w, b2.x, dx, dy, sigma, vis);
       unsigned long long mv[PPL];
-      if (bwd_taken<PPL>(b2.y, vis, sigma, li, bin_final, alpha, mv) == 0ull) continue;
-      bool v[PPL];
-      bwd_recur<PPL>(mv, alpha, T_cur, v, ra, fac);
+      if (bwd_taken<PPL>(b2.y, vis, sigma, li, bin_final, raw, mv) == 0ull) continue;
+      bwd_recur<PPL>(mv, raw, T_cur, alpha, ra, fac);
       // w = <colour, v_out> over this chunk's channels (see bwd_moments)
       const float* col = s_col + t * CK;
       fv w = 0.f;
 #pragma unroll
       for (int c = 0; c < CK; ++c) w += col[c] * vo[c];
       fv gop, gy, gyy;
-      bwd_moments<PPL>(vis, w, T_cur, alpha, v, dy, R, gop, gy, gyy);
+      bwd_moments<PPL>(raw, w, T_cur, alpha, dy, R, gop, gy, gyy);
       float s[kRow];
 #pragma unroll
       for (int c = 0; c < CK; ++c) {
@@ -323,7 +322,8 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
       const size_t g = goff + (size_t)s_id[t];
       const float4 a4 = s_a[t];
       const float2 b2 = s_b[t];
-      const float nop = -b2.y;   // d loss / d sigma = -opacity * gop: moments of gop -> sigma sums
+      // moments of gop = opacity e v_alpha (bwd_moments): d loss / d sigma = -gop, so the sigma sums are the negated moments,
+      // and v_opacity = m0 / opacity -- a true division; a touched entry was taken with opacity e >= 1/255, so opacity > 0
       const float3 cn = true_conic(a4.z, a4.w, b2.x);
       const float ca = cn.x, cb = cn.y, cc = cn.z;
       int k1 = k, k2 = k;
@@ -335,8 +335,8 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
         const int m = k - CK;
         k1 = (m == 1 || m == 2) ? CK + 1 : k;
         k2 = CK + 2;
-        w1 = (m == 0) ? 1.f : (m == 1) ? nop * ca : (m == 2) ? nop * cb : (m == 4) ? nop : 0.5f * nop;
-        w2 = (m == 1) ? nop * cb : (m == 2) ? nop * cc : 0.f;
+        w1 = (m == 0) ? 1.f : (m == 1) ? -ca : (m == 2) ? -cb : (m == 4) ? -1.f : -0.5f;
+        w2 = (m == 1) ? -cb : (m == 2) ? -cc : 0.f;
         dst = (m == 0) ? v_opacity + g : (m <= 2) ? v_xy + 2 * g + (m - 1) : v_conic + 3 * g + (m - 3);
       }
       float s1 = 0.f, s2 = 0.f;
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(64 * Pix<PPL>::kWaves) void raster_nd_bwd_kernel(
         s1 += tw ? s_acc[w][t][k1] : 0.f;
         s2 += tw ? s_acc[w][t][k2] : 0.f;
       }
-      atomicAdd(dst, w1 * s1 + w2 * s2);
+      atomicAdd(dst, k == CK ? s1 / b2.y : w1 * s1 + w2 * s2);
     }
   }
 }

@@ -44,6 +44,10 @@ int gol_selftest_wave_sum4(const float* in256, float* out128, void* stream);
 /* The 8-way reduction: in512 = 8 x 64 floats (a0 .. a7 per lane); out64 = its per-lane result.  Lane 16 r + 7 holds
  * sum(a_r) and lane 16 r + 15 sum(a_{4+r}), r = 0..3; the other lanes hold partial sums. */
 int gol_selftest_wave_sum8(const float* in512, float* out64, void* stream);
+/* The column-first reduction of the two-pixel raster backward: in384 = 6 x 64 floats (s0, s1, s2, m0, my, myy per lane),
+ * dx64 = the factor dx of every lane, equal in lanes l and l + 16; out64 = its per-lane result.  Lanes 7, 39, 23, 55 hold
+ * sum(s0), sum(s1), sum(s2), sum(myy); lanes 15, 31, 47, 63 sum(m0), sum(dx m0), sum(my), sum(dx my); lane 19 sum(dx^2 m0). */
+int gol_selftest_wave_colsum(const float* in384, const float* dx64, float* out64, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * sgutils -- spherical-Gaussian specular lobe evaluation.
