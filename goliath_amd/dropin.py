@@ -547,7 +547,8 @@ REGULARIZER_LOSSES = ("bound_primscale", "negcolor", "l2_reg", "list_l1_reg", "b
 IMAGE_LOSSES = ("rgb_l2", "psnr", "rgb_l1_focus", "rgb_l1_phys", "pose_shadow_l2")
 
 
-def patch_losses(registry_module=None, regularizers=False, images=False, perceptual=None, effnet=None):
+def patch_losses(registry_module=None, regularizers=False, images=False, perceptual=None, effnet=None,
+                 perceptual_precision="fp32"):
     """Re-register the image losses of the reference's loss registry (ca_code/loss/registry.py:59-79; rgb_l1 and
     rgb_ssim, ca_code/loss/__init__.py:391-411, 478-494) with the fused HIP versions, so a `ModularLoss` built from the
     unchanged config picks them up.  Call after `import ca_code.loss` and before constructing the loss.
@@ -558,7 +559,8 @@ def patch_losses(registry_module=None, regularizers=False, images=False, percept
     torchvision vgg19 state dict, the path of one or a goliath_amd.perceptual.Vgg19Features also re-registers `vgg`
     (ca_code/loss/perceptual.py:55-58) with goliath_amd.perceptual.VGGLoss over that network (gol_conv3_* where the layer's
     shape is in perceptual.DISPATCH); the weights come from the caller, nothing is downloaded, and the default (None)
-    leaves `vgg` untouched.  effnet= a torchvision efficientnet_b0 state dict, the path of one or a
+    leaves `vgg` untouched; perceptual_precision="bf16x3" (opt-in, passed to perceptual.as_features) runs its wide layers on
+    the split-bf16 operator gol_conv3x_* where perceptual.DISPATCH_BF16X3 admits the shape.  effnet= a torchvision efficientnet_b0 state dict, the path of one or a
     goliath_amd.effnet.EffNetB0Features also re-registers `effnet` and `effnet_phys` (ca_code/loss/perceptual.py:61-69; the
     latter with src_key="rendered_phys_rgb") with goliath_amd.effnet.EffNetLoss over ONE shared network
     (gol_mbconv_front_* where the block's shape is in effnet.DISPATCH), without importing ca_code.loss.effnet or
@@ -584,7 +586,7 @@ def patch_losses(registry_module=None, regularizers=False, images=False, percept
     if perceptual is not None:
         from . import perceptual as perceptual_module
 
-        features = perceptual_module.as_features(perceptual)
+        features = perceptual_module.as_features(perceptual, perceptual_precision)
         registry_module.loss_registry["vgg"] = \
             lambda assets=None, **kwargs: perceptual_module.VGGLoss(assets, features=features, **kwargs)
     if effnet is not None:

@@ -705,6 +705,36 @@ int gol_conv3_bwd_x(int B, int Ci, int Co, int H, int W, int image_in, int pool,
                     const float* y, const unsigned char* pos, const float* g_y, float* g_x, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * gol_conv3x_pack / gol_conv3x_fwd / gol_conv3x_bwd_x: the layer of gol_conv3_fwd / gol_conv3_bwd_x (without image_in) at
+ * precision "bf16x3": a split-bf16 product on v_mfma_f32_16x16x32_bf16, for the wide layers of the network.
+ *   split(v): hi = bf16_rne(v), lo = bf16_rne(v - float(hi))      (round to nearest even; the subtraction is exact in fp32)
+ *   acc[b,co,r,c] = sum_{ci,ky,kx} (lo_x hi_w + hi_x lo_w + hi_x hi_w)    over xpad[b,ci,r-1+ky,c-1+kx], weight[co,ci,ky,kx]
+ *   Products are exact, the sum is fp32, the lo lo term is dropped: |acc - exact| <= 3.1 2^-16 sum |x||w|, 4.5e-6 rel-L2
+ *   measured against float64.  Inputs are finite and of ordinary magnitude: a subnormal lo is not handled (it may be
+ *   flushed), inf / NaN are not defined.  Zero padding splits to (0, 0).
+ * gol_conv3x_pack splits the weight ONCE into packed[gol_conv3x_packed_elems(Co, Ci)] (16-bit elements, 16-byte aligned):
+ *   [hi | lo][tap][Co / 8][Ci / 8][8 co][8 ci].  The same buffer serves both directions: the forward reads a block's rows,
+ *   the backward transposes the block on its way to LDS and mirrors the taps.  gol_conv3x_packed_elems returns 0 for an
+ *   unsupported (Co, Ci).
+ * gol_conv3x_fwd: x [B,Ci,H,W] is split while it is loaded; y = relu(acc + bias[co]) [B,Co,H,W], or with pool only
+ *   p [B,Co,H/2,W/2] and pos (bytes): gol_conv3_fwd's semantics -- 2x2 max, stride 2, floor; pos = the window position of
+ *   the maximum, 0..3 row-major, the first maximum in that order wins; a last odd row or column feeds nothing.
+ * gol_conv3x_bwd_x: gol_conv3_bwd_x's: y = the forward's y, or p with pool (then g_y is g_p and pos the forward's bytes);
+ *   g_pre = g_y where y > 0 (with pool: g_p where pos names the element and p > 0), else 0, formed while loading and THEN
+ *   split; g_x [B,Ci,H,W] written = the transposed convolution of g_pre in the same three products.
+ * Supported: Ci % 32 == 0, Co % 32 == 0, any H, W >= 1 (>= 2 with pool), B <= 65535: everything else returns
+ * GOL_ERR_UNSUPPORTED (there is no image layer: Ci = 3 stays on gol_conv3_fwd).  A null pointer with positive sizes returns
+ * GOL_ERR_INVALID_ARG; B == 0 returns GOL_OK without a launch.  No atomics, no scratch, no host sync, no allocation: one
+ * launch each, bitwise reproducible, capturable as a linear graph.
+ * ---------------------------------------------------------------------------------------- */
+long long gol_conv3x_packed_elems(int Co, int Ci);
+int gol_conv3x_pack(int Co, int Ci, const float* weight, unsigned short* packed, void* stream);
+int gol_conv3x_fwd(int B, int Ci, int Co, int H, int W, int pool, const float* x, const unsigned short* packed,
+                   const float* bias, float* y, unsigned char* pos, void* stream);
+int gol_conv3x_bwd_x(int B, int Ci, int Co, int H, int W, int pool, const unsigned short* packed, const float* y,
+                     const unsigned char* pos, const float* g_y, float* g_x, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * gol_mbconv_front_fwd / gol_mbconv_front_bwd_x: the front of an MBConv block of the frozen EfficientNet-B0 feature
  * network of the `effnet` / `effnet_phys` losses (ca_code/loss/effnet.py:45-51 runs torchvision's
  * efficientnet_b0().features[0:4]; registered at ca_code/loss/perceptual.py:60-69): expand 1x1 + BN + SiLU, depthwise
