@@ -41,6 +41,7 @@ _SYMBOLS = [
     "gol_uvframes_bwd_scratch_floats", "gol_uvframes_fwd", "gol_uvframes_bwd",
     "gol_upconv_fwd", "gol_upconv_bwd_scratch_floats", "gol_upconv_bwd",
     "gol_upcat_conv_fwd", "gol_upcat_conv_bwd_scratch_floats", "gol_upcat_conv_bwd",
+    "gol_featenc_front_fwd", "gol_featenc_front_bwd_scratch_floats", "gol_featenc_front_bwd",
     "gol_uvtex_partial_floats", "gol_uvtex_fwd", "gol_uvtex_bwd", "gol_pack_rgba_fwd", "gol_pack_rgba_bwd",
     "gol_normal_rgba",
     "gol_olat_features_fwd", "gol_olat_combine_fwd", "gol_olat_combine_bwd",

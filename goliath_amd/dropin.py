@@ -625,7 +625,7 @@ def patch_image_ops(*modules):
 
 
 def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, texture_decoder=False, texture_tail=False,
-                 displacement_unet=False):
+                 displacement_unet=False, feat_encoder=False):
     """BASELINE config 4 as a drop-in: `ConvTeacherDecoder.forward` (ca_code/models/urhand.py:349-630) with its two light
     loops and both shadow-map evaluations on the HIP kernels (goliath_amd.urhand.conv_teacher_decoder_forward) and the
     stand-alone shadow-map lookup (`get_shadow_map`, imported at urhand.py:44).  The depth images of the light cameras are
@@ -674,8 +674,18 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, t
     (gol_upcat_conv_fwd / _bwd: neither the upsampled nor the concatenated tensor exists in memory) where its shape is in
     dispunet.DISPATCH, and runs the reference's lines everywhere else.  Opt-in: the default binding clears the flag and is
     unchanged.  Measured per level and for the whole UNet by tools/dispunet_probe.py (profiles/dispunet_probe.json,
-    DESIGN.md section 6c-bis).  Returns the patched module."""
-    from . import dispunet, meshraster, shadowmap, texdec, urhand, uvtex
+    DESIGN.md section 6c-bis).
+
+    feat_encoder=True sets `featenc.FEATENC_FLAG` on the decoder class: either forward then runs its feature encoder
+    (`self.featenc`, urhand.py:302; FeatEncoderUNet.forward, :98-107, called at :585 on `feat_p.detach()`) through
+    goliath_amd.featenc.forward, provided it has `proj`, `feat_mod`, `gb_mod` and `enc` (any other encoder is called as a
+    module, as today).  The 7x7 projection and the first 4x4 / stride 2 layer -- both weight-normalised, without bias --
+    go to the fused operator (gol_featenc_front_fwd / _bwd: the 64-channel tensor between them and its gradient never
+    exist in memory) where the shape is in featenc.DISPATCH, and run the reference's two lines everywhere else; every
+    later layer runs as the reference's.  Opt-in: the default binding clears the flag and is unchanged.  Measured for the
+    pair and for the whole encoder by tools/featenc_probe.py (profiles/featenc_probe.json).
+    Returns the patched module."""
+    from . import dispunet, featenc, meshraster, shadowmap, texdec, urhand, uvtex
 
     if urhand_module is None:
         import ca_code.models.urhand as urhand_module
@@ -701,6 +711,7 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, t
                                                 else urhand.conv_teacher_decoder_forward)
     setattr(urhand_module.ConvTeacherDecoder, texdec.TEXTURE_DECODER_FLAG, bool(texture_decoder))
     setattr(urhand_module.ConvTeacherDecoder, dispunet.DISPLACEMENT_UNET_FLAG, bool(displacement_unet))
+    setattr(urhand_module.ConvTeacherDecoder, featenc.FEATENC_FLAG, bool(feat_encoder))
     ae = urhand_module.AutoEncoder if texture_tail else getattr(urhand_module, "AutoEncoder", None)
     if texture_tail:
         if "_gol_reference_forward" not in ae.__dict__:

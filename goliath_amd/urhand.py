@@ -17,6 +17,9 @@
     either forward, where the decoder class carries dispunet.DISPLACEMENT_UNET_FLAG (dropin.patch_urhand(displacement_unet=True)):
         * the decoder levels of the displacement / roughness UNet (:217-226, :231-239): leaky + 2x bilinear resize + concat +
           weight-normalised 3x3 conv (+ tanh head)     -> gol_upcat_conv_fwd/bwd (goliath_amd.dispunet), per shape, opt-in
+    either forward, where the decoder class carries featenc.FEATENC_FLAG (dropin.patch_urhand(feat_encoder=True)):
+        * the 7x7 projection and the first 4x4 / stride 2 layer of the feature encoder (:100-102, called at :585)
+                                                     -> gol_featenc_front_fwd/bwd (goliath_amd.featenc), per shape, opt-in
     olat_rgb_decoder_forward_rgb   <- /root/reference/ca_code/models/hand_teacher_mvp.py:253-494
         * the deep-shadow march (:271-358: L-fold copies of the primitive set and of a 4-channel template, an ordinary
           ray march with with_shadow=True) -> gol_mvp_shadow_march (all lights of a frame share transforms, tree and an
@@ -46,7 +49,7 @@ from typing import List, Optional
 import torch
 import torch.nn.functional as F
 
-from . import _lib, dispunet, meshraster, mvp, mvpprims, olat, shadowmap, texdec, uvframes, uvlight, uvtex
+from . import _lib, dispunet, featenc, meshraster, mvp, mvpprims, olat, shadowmap, texdec, uvframes, uvlight, uvtex
 from .imgtail import cal_v5_matrix
 
 
@@ -223,7 +226,12 @@ def _decoder_forward(self, fused_frames, lbs_motion, id_mesh, tex_mean, verts_re
         id_pose_feat = torch.cat([id_pose_feat, viewout], dim=1)
     outputs.update(id_pose_conv=id_pose_feat)
     joint_feat = self.joint_conv_block_tex(id_pose_feat)
-    z, gainbias = self.featenc(feat_p.detach().reshape(B, -1, feat_p.shape[-2], feat_p.shape[-1]))
+    feat_in = feat_p.detach().reshape(B, -1, feat_p.shape[-2], feat_p.shape[-1])
+    if (getattr(type(self), featenc.FEATENC_FLAG, False)                  # dropin.patch_urhand(feat_encoder=True)
+            and all(hasattr(self.featenc, a) for a in ("proj", "feat_mod", "gb_mod", "enc"))):
+        z, gainbias = featenc.forward(self.featenc, feat_in)
+    else:
+        z, gainbias = self.featenc(feat_in)
     if getattr(type(self), texdec.TEXTURE_DECODER_FLAG, False):   # dropin.patch_urhand(texture_decoder=True)
         x = texdec.texture_branches(self, joint_feat, z, gainbias)
     else:

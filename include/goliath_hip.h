@@ -671,6 +671,41 @@ int gol_upcat_conv_bwd(int B, int Ca, int Cb, int Co, int Hi, int Wi, int act, f
                        const float* g_y, float* g_xa, float* g_xb, float* g_w, float* g_bias, float* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Front of URHand's FeatEncoderUNet as one operator: the weight-normalised 7x7 / stride 1 / pad 3 projection and the
+ * first 4x4 / stride 2 / pad 1 feature layer, both without bias and with nothing between them.  Replaces, in
+ * FeatEncoderUNet.forward (ca_code/models/urhand.py:100-102; layers built at :91-93 from la.Conv2dWN(.., bias=False),
+ * ca_code/nn/layers.py:470),
+ *   x = self.proj(x); x = self.feat_mod[0](x)
+ * two MIOpen convolutions and, backward, their weight-gradient convolutions and the input gradient of the second:
+ *   h[b,m,r,c]  = sum_{cx,ky,kx} xpad[b,cx,r-3+ky,c-3+kx] w_p[m,cx,ky,kx]     0 <= r < H, 0 <= c < W; xpad = x inside the
+ *                                                                               image, 0 outside
+ *   y[b,co,Y,X] = sum_{m,ky,kx}  hpad[b,m,2Y-1+ky,2X-1+kx] w_f[co,m,ky,kx]    hpad = h inside the image and EXACTLY 0
+ *                                                                               outside (not the 7x7 response of the
+ *                                                                               zero-extended x at positions out there)
+ *   x [B,Cx,H,W]; w_p [Cm,Cx,7,7] and w_f [Co,Cm,4,4] are EFFECTIVE weights (the weight norm already applied,
+ *   goliath_amd/tail.py:wn_weight); y [B,Co,H/2,W/2].  fp32 MFMA (v_mfma_f32_16x16x4_f32) in both GEMMs, exact fp32.
+ *   h never exists in memory: nothing but y is written.
+ * bwd produces the two weight gradients only -- the operator has no input gradient (the model feeds it a detached
+ * tensor, urhand.py:585); either output may be NULL = not wanted, at no cost, the other one bitwise unchanged:
+ *   g_w_f [Co,Cm,4,4] written = sum_{b,Y,X} g_y[b,co,Y,X] hpad[b,m,2Y-1+ky,2X-1+kx], h recomputed from x; needs x, w_p;
+ *   g_w_p [Cm,Cx,7,7] written = sum_{b,r,c} g_h[b,m,r,c] xpad[b,cx,r-3+ky,c-3+kx], g_h = the stride-2 transposed
+ *       convolution of g_y with w_f restricted to the image, formed per tile on chip, never written; needs x, w_f.
+ *   Both need scratch[gol_featenc_front_bwd_scratch_floats]: a workgroup owns a block of the weight and walks a run of
+ *   tiles, its partial sum leaves once and a second kernel adds the partials in a fixed order (no float atomics, bitwise
+ *   reproducible).  4 -> 64 -> 192 at 1024^2, B = 1: 9,961,472 floats = 38.0 MiB.
+ * Supported: Cx in 1..8 (the K stage is zero-padded on the weight side: no channel of x that does not exist is read),
+ * Cm % 16 == 0, Co % 16 == 0, H and W even and >= 2, B <= 65535: everything else returns GOL_ERR_UNSUPPORTED
+ * (gol_featenc_front_bwd_scratch_floats: 0).  A null pointer with positive sizes returns GOL_ERR_INVALID_ARG; B == 0
+ * returns GOL_OK without a launch (bwd: the outputs it is given are zeroed).  w_f must be 16-byte aligned.  No host sync,
+ * no allocation: both calls can be captured as a linear graph.
+ * ---------------------------------------------------------------------------------------- */
+int gol_featenc_front_fwd(int B, int Cx, int Cm, int Co, int H, int W, const float* x, const float* w_p,
+                          const float* w_f, float* y, void* stream);
+long long gol_featenc_front_bwd_scratch_floats(int B, int Cx, int Cm, int Co, int H, int W);
+int gol_featenc_front_bwd(int B, int Cx, int Cm, int Co, int H, int W, const float* x, const float* w_p,
+                          const float* w_f, const float* g_y, float* g_w_p, float* g_w_f, float* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * gol_conv3_fwd / gol_conv3_bwd_x: a layer of the frozen VGG19 feature network of the masked perceptual loss
  * (ca_code/loss/vgg.py:17-88; `vgg`, ca_code/loss/perceptual.py:55-58) as one operator: 3x3 / stride 1 / zero padding 1
  * convolution + bias + ReLU, optionally on the normalised image and optionally followed by the 2x2 max-pool.  Replaces
