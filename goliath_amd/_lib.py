@@ -48,6 +48,8 @@ _SYMBOLS = [
     "gol_mvp_tail_fwd", "gol_mvp_tail_bwd_scratch_floats", "gol_mvp_tail_bwd",
     "gol_conv3_fwd", "gol_conv3_bwd_x",
     "gol_conv3x_packed_elems", "gol_conv3x_pack", "gol_conv3x_fwd", "gol_conv3x_bwd_x",
+    "gol_conv4x_packed_elems", "gol_conv4x_pack", "gol_conv4x_fwd", "gol_conv4x_bwd_x", "gol_conv4x_bwd_w_scratch_floats",
+    "gol_conv4x_bwd_w",
     "gol_mbconv_front_tiles", "gol_mbconv_front_fwd", "gol_mbconv_front_bwd_x",
 ]
 

@@ -26,14 +26,9 @@
 //             g_p     backward with pool: g_pre[r,c] = g_p[r/2,c/2] where the position byte names (r,c) and p > 0, else 0
 //   epilogues relu, pool (first maximum wins, one position byte per pooled element, floor pool), g_x: as in vggconv.hip
 // No atomics, no scratch: every output element is written by exactly one lane from a fixed-order sum -- bitwise reproducible.
-#include "gol_common.h"
+#include "gol_splitbf16.h"  // the vector types, cx_split and cx_slot (shared with conv4x.hip)
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct CxDims {
   int B, M, K, H, W, Hp, Wp;  // M rows of the GEMM (channels written), K reduction channels (channels read), pooled size
@@ -46,15 +41,6 @@ constexpr int kKS = 32;                      // channels per K stage = the K of 
 
 enum { L_PLAIN = 0, L_GY = 2, L_GP = 3 };
 enum { E_RELU = 0, E_POOL = 1, E_GX = 2 };
-
-// the 16-byte slot (0..3) of chunk q in row n of an LDS image with 64-byte rows
-__device__ __forceinline__ int cx_slot(int n, int q) { return q ^ ((n >> 1) & 2); }
-
-// v = hi + lo + O(2^-16 |v|), both bf16 by round to nearest even
-__device__ __forceinline__ void cx_split(const f32x8 v, bf16x8& hi, bf16x8& lo) {
-  hi = __builtin_convertvector(v, bf16x8);
-  lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x8), bf16x8);
-}
 
 // 32 channels of the haloed window, origin (r0 - 1, c0 - 1), split into s_in[hi|lo][position][32]; outside the image: zeros.
 // An item = one window position x 8 channels; the loads are unconditional (clamped to element 0, the value is dropped).

@@ -625,7 +625,7 @@ def patch_image_ops(*modules):
 
 
 def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, texture_decoder=False, texture_tail=False,
-                 displacement_unet=False, feat_encoder=False):
+                 displacement_unet=False, feat_encoder=False, feat_encoder_precision="fp32"):
     """BASELINE config 4 as a drop-in: `ConvTeacherDecoder.forward` (ca_code/models/urhand.py:349-630) with its two light
     loops and both shadow-map evaluations on the HIP kernels (goliath_amd.urhand.conv_teacher_decoder_forward) and the
     stand-alone shadow-map lookup (`get_shadow_map`, imported at urhand.py:44).  The depth images of the light cameras are
@@ -684,6 +684,11 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, t
     exist in memory) where the shape is in featenc.DISPATCH, and run the reference's two lines everywhere else; every
     later layer runs as the reference's.  Opt-in: the default binding clears the flag and is unchanged.  Measured for the
     pair and for the whole encoder by tools/featenc_probe.py (profiles/featenc_probe.json).
+    feat_encoder_precision ("fp32" by default, or "bf16x3") is stored next to the flag as
+    `featenc.FEATENC_PRECISION_FLAG` and handed to featenc.forward: at "bf16x3" the bias-free 4x4 / stride 2 layers
+    `feat_mod[0..3]` whose shape is in featenc.DISPATCH_BF16X3 run on the split-bf16 operator featenc.conv4s2
+    (gol_conv4x_*: forward, input gradient and weight gradient; tools/conv4x_probe.py, profiles/conv4x_probe.json,
+    DESIGN.md section 6c-quater).  It has no effect without feat_encoder=True; an unknown value raises ValueError.
     Returns the patched module."""
     from . import dispunet, featenc, meshraster, shadowmap, texdec, urhand, uvtex
 
@@ -712,6 +717,7 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, t
     setattr(urhand_module.ConvTeacherDecoder, texdec.TEXTURE_DECODER_FLAG, bool(texture_decoder))
     setattr(urhand_module.ConvTeacherDecoder, dispunet.DISPLACEMENT_UNET_FLAG, bool(displacement_unet))
     setattr(urhand_module.ConvTeacherDecoder, featenc.FEATENC_FLAG, bool(feat_encoder))
+    setattr(urhand_module.ConvTeacherDecoder, featenc.FEATENC_PRECISION_FLAG, featenc._precision(feat_encoder_precision))
     ae = urhand_module.AutoEncoder if texture_tail else getattr(urhand_module, "AutoEncoder", None)
     if texture_tail:
         if "_gol_reference_forward" not in ae.__dict__:

@@ -229,7 +229,8 @@ def _decoder_forward(self, fused_frames, lbs_motion, id_mesh, tex_mean, verts_re
     feat_in = feat_p.detach().reshape(B, -1, feat_p.shape[-2], feat_p.shape[-1])
     if (getattr(type(self), featenc.FEATENC_FLAG, False)                  # dropin.patch_urhand(feat_encoder=True)
             and all(hasattr(self.featenc, a) for a in ("proj", "feat_mod", "gb_mod", "enc"))):
-        z, gainbias = featenc.forward(self.featenc, feat_in)
+        z, gainbias = featenc.forward(self.featenc, feat_in,
+                                      precision=getattr(type(self), featenc.FEATENC_PRECISION_FLAG, "fp32"))
     else:
         z, gainbias = self.featenc(feat_in)
     if getattr(type(self), texdec.TEXTURE_DECODER_FLAG, False):   # dropin.patch_urhand(texture_decoder=True)

@@ -770,6 +770,44 @@ int gol_conv3x_bwd_x(int B, int Ci, int Co, int H, int W, int pool, const unsign
                      const unsigned char* pos, const float* g_y, float* g_x, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * gol_conv4x_*: a linear, bias-free 4x4 / stride 2 / zero padding 1 convolution at precision "bf16x3" (the split product
+ * of gol_conv3x_*, on v_mfma_f32_16x16x32_bf16) with forward, input gradient and weight gradient: the feature layers
+ * feat_mod[0..3] of URHand's FeatEncoderUNet on their EFFECTIVE weights.  Replaces, in FeatEncoderUNet.forward
+ * (ca_code/models/urhand.py:102; layers built at :93 from la.Conv2dWN(n_in, n_out, 4, 2, 1, bias=False),
+ * ca_code/nn/layers.py:470),
+ *   x = self.feat_mod[i](x)
+ * one fp32 MIOpen convolution and, backward, its input-gradient and weight-gradient convolutions:
+ *   y  [b,co,Y,X]     = sum_{ci,ky,kx} xpad[b,ci,2Y-1+ky,2X-1+kx] w[co,ci,ky,kx]      xpad = x inside the image, 0 outside
+ *   g_x[b,ci,r,c]     = sum_{co,ky,kx} g_y[b,co,Y,X] w[co,ci,ky,kx]                   over 2Y-1+ky = r, 2X-1+kx = c
+ *   g_w[co,ci,ky,kx]  = sum_{b,Y,X}    g_y[b,co,Y,X] xpad[b,ci,2Y-1+ky,2X-1+kx]
+ *   x [B,Ci,H,W]; w, g_w [Co,Ci,4,4]; y, g_y [B,Co,H/2,W/2]; g_x [B,Ci,H,W].  Every product a b is
+ *   lo_a hi_b + hi_a lo_b + hi_a hi_b with split(v): hi = bf16_rne(v), lo = bf16_rne(v - float(hi)); BOTH operands of all
+ *   three directions are split (x and g_y while they are staged); products are exact, the sum is fp32, lo lo is dropped:
+ *   |result - exact| <= 3.1 2^-16 sum |a||b|.  Inputs finite and of ordinary magnitude, as for gol_conv3x_*.
+ * gol_conv4x_pack splits w ONCE per call into packed[gol_conv4x_packed_elems(Co, Ci)] (16-bit elements, 16-byte aligned):
+ *   [hi | lo][16 taps][Co / 8][Ci / 8][8 co][8 ci]; the same buffer serves fwd and bwd_x (which transposes a block on its way
+ *   to LDS).  gol_conv4x_packed_elems returns 0 for an unsupported (Co, Ci).
+ * gol_conv4x_bwd_x: g_x written (8-byte aligned); g_x == NULL: no launch.
+ * gol_conv4x_bwd_w: reads the fp32 x and g_y; K (the pixels) is split over workgroups, whose partials go to
+ *   scratch[gol_conv4x_bwd_w_scratch_floats] and are added in block order by a second kernel (no float atomics).  The scratch
+ *   is blocks x 16 Co Ci floats with blocks = about 512 / ((Ci / 32) ceil(Co / 64)), at most one per 32 output pixels of a
+ *   row: never more than (512 + (Ci / 32) ceil(Co / 64)) x 32768 floats, whatever B, H and W.  g_w == NULL: no launch.
+ * Supported: Ci % 32 == 0, Co % 32 == 0, H and W even and >= 2, B <= 65535: everything else returns GOL_ERR_UNSUPPORTED
+ * before any launch (gol_conv4x_bwd_w_scratch_floats: 0).  A null pointer that is needed returns GOL_ERR_INVALID_ARG;
+ * B == 0 returns GOL_OK without a kernel (bwd_w zeroes g_w).  Offsets are 64-bit across planes.  Every output element is a
+ * fixed-order sum: bitwise reproducible.  No host sync, no allocation: capturable as a linear graph.
+ * ---------------------------------------------------------------------------------------- */
+long long gol_conv4x_packed_elems(int Co, int Ci);
+int gol_conv4x_pack(int Co, int Ci, const float* weight, unsigned short* packed, void* stream);
+int gol_conv4x_fwd(int B, int Ci, int Co, int H, int W, const float* x, const unsigned short* packed, float* y,
+                   void* stream);
+int gol_conv4x_bwd_x(int B, int Ci, int Co, int H, int W, const unsigned short* packed, const float* g_y, float* g_x,
+                     void* stream);
+long long gol_conv4x_bwd_w_scratch_floats(int B, int Ci, int Co, int H, int W);
+int gol_conv4x_bwd_w(int B, int Ci, int Co, int H, int W, const float* x, const float* g_y, float* g_w, float* scratch,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * gol_mbconv_front_fwd / gol_mbconv_front_bwd_x: the front of an MBConv block of the frozen EfficientNet-B0 feature
  * network of the `effnet` / `effnet_phys` losses (ca_code/loss/effnet.py:45-51 runs torchvision's
  * efficientnet_b0().features[0:4]; registered at ca_code/loss/perceptual.py:60-69): expand 1x1 + BN + SiLU, depthwise
