@@ -50,6 +50,8 @@ _SYMBOLS = [
     "gol_conv3x_packed_elems", "gol_conv3x_pack", "gol_conv3x_fwd", "gol_conv3x_bwd_x",
     "gol_conv4x_packed_elems", "gol_conv4x_pack", "gol_conv4x_fwd", "gol_conv4x_bwd_x", "gol_conv4x_bwd_w_scratch_floats",
     "gol_conv4x_bwd_w",
+    "gol_conv3ub_packed_elems", "gol_conv3ub_pack", "gol_conv3ub_fwd", "gol_conv3ub_bwd_x",
+    "gol_conv3ub_bwd_w_scratch_floats", "gol_conv3ub_bwd_w", "gol_conv3ub_bwd_bias",
     "gol_mbconv_front_tiles", "gol_mbconv_front_fwd", "gol_mbconv_front_bwd_x",
 ]
 

@@ -731,16 +731,24 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, t
     return urhand_module
 
 
-def patch_hand_teacher(teacher_module=None, olat_fused=False):
+def patch_hand_teacher(teacher_module=None, olat_fused=False, unet_precision="fp32"):
     """BASELINE config 5's teacher as a drop-in: `OLATRGBDecoder.forward_rgb` (ca_code/models/hand_teacher_mvp.py:253-494)
     with the per-light deep-shadow march on gol_mvp_shadow_march (goliath_amd.urhand.olat_rgb_decoder_forward_rgb).
     olat_fused=True binds urhand.olat_rgb_decoder_forward_rgb_fused instead: the UNet input and the OLAT sum on
     gol_olat_features_fwd / gol_olat_combine_fwd / _bwd as well (goliath_amd.olat); a later call with False restores the default.
+    unet_precision ("fp32" by default, or "bf16x3") is stored on the class as `olatunet.UNET_PRECISION_FLAG` and handed to
+    goliath_amd.olatunet.forward by the fused forward: at "bf16x3" a UNet level (:444-467: th.cat + Conv2dWNUB 3x3 + untied
+    bias + LeakyReLU) whose shape is in olatunet.DISPATCH runs on the split-bf16 operator olatunet.conv3_ub_lrelu
+    (gol_conv3ub_*: forward and the gradients to both inputs, the weight and the bias, without the concatenated tensor;
+    tools/olatunet_probe.py, profiles/olatunet_probe.json).  It has no effect without
+    olat_fused=True; an unknown value raises ValueError.
     The ordinary ray march of the model already runs on the HIP kernels through `install()` (mvpraymarchlib / utilslib)."""
-    from . import urhand
+    from . import olatunet, urhand
 
+    unet_precision = olatunet._precision(unet_precision)
     if teacher_module is None:
         import ca_code.models.hand_teacher_mvp as teacher_module
+    setattr(teacher_module.OLATRGBDecoder, olatunet.UNET_PRECISION_FLAG, unet_precision)
     teacher_module.OLATRGBDecoder.forward_rgb = (urhand.olat_rgb_decoder_forward_rgb_fused if olat_fused
                                                  else urhand.olat_rgb_decoder_forward_rgb)
     return teacher_module

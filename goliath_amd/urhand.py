@@ -29,6 +29,9 @@
                                                           -> gol_olat_features_fwd (goliath_amd.olat), opt-in
         * the OLAT sum (:468-488: sigmoid, 25 t + 100, relu, intensities, sum over lights, primshadow)
                                                           -> gol_olat_combine_fwd/bwd, opt-in (dropin.patch_hand_teacher(olat_fused=True))
+        * the UNet between them (:444-467: per level th.cat + Conv2dWNUB 3x3 + untied bias + LeakyReLU)
+                                                          -> gol_conv3ub_* (goliath_amd.olatunet), per shape, opt-in
+                                                             (patch_hand_teacher(olat_fused=True, unet_precision="bf16x3"))
 
     autoencoder_forward   <- /root/reference/ca_code/models/urhand.py:750-990 (AutoEncoder.forward with forward_tex,
         :711-748); where the model's class carries uvtex.TEXTURE_TAIL_FLAG (dropin.patch_urhand(texture_tail=True)):
@@ -49,7 +52,8 @@ from typing import List, Optional
 import torch
 import torch.nn.functional as F
 
-from . import _lib, dispunet, featenc, meshraster, mvp, mvpprims, olat, shadowmap, texdec, uvframes, uvlight, uvtex
+from . import (_lib, dispunet, featenc, meshraster, mvp, mvpprims, olat, olatunet, shadowmap, texdec, uvframes, uvlight,
+               uvtex)
 from .imgtail import cal_v5_matrix
 
 
@@ -571,7 +575,9 @@ def olat_rgb_decoder_forward_rgb_fused(
 ):
     """`olat_rgb_decoder_forward_rgb` with the work around the UNet on csrc/olat.hip: same arguments, same output dict.
     The UNet input comes from one gol_olat_features_fwd (hand_teacher_mvp.py:371-439) and the OLAT sum from
-    gol_olat_combine_fwd / _bwd (:468-488); the deep shadow and the UNet are the unfused function's.  The UNet input does
+    gol_olat_combine_fwd / _bwd (:468-488); the deep shadow is the unfused function's, and the UNet (:444-467) runs through
+    goliath_amd.olatunet.forward at the precision of the class flag `olatunet.UNET_PRECISION_FLAG` ("fp32" unless
+    dropin.patch_hand_teacher(unet_precision="bf16x3") set it: the unfused function's lines).  The UNet input does
     not require grad (goliath_amd.olat.features).  With an input on the CPU, or a light_intensity that requires grad (the
     combine has no gradient for it), the unfused function runs instead."""
     tensors = (campos, primpos, primrot, primscale, primalpha, valid_prims, joint_feat, light_pos, light_intensity)
@@ -591,19 +597,8 @@ def olat_rgb_decoder_forward_rgb_fused(
         x = olat.features(f32(primpos), f32(primrot), f32(primscale), f32(valid_prims), f32(light_pos), f32(campos), shadow,
                           self.primsize, self.n_prim_x, self.n_prim_y, self.volradius)
     joint_feat = joint_feat[:, None].expand(-1, L, -1, -1, -1).reshape(B * L, *joint_feat.shape[-3:])
-    enc_acts = []
-    for i, layer in enumerate(self.enc_layers):          # UNet encoder
-        x = layer(x)
-        enc_acts.append(x)
-        if i < len(self.sizes) - 1:
-            x = F.interpolate(x, scale_factor=0.5, mode="bilinear", recompute_scale_factor=True, align_corners=True)
-    for i, layer in enumerate(self.dec_layers):          # UNet decoder with skip connections
-        if i == 0:
-            x = torch.cat([x, joint_feat], dim=1)
-        else:
-            skip = enc_acts[-i - 1]
-            x = torch.cat([F.interpolate(x, size=skip.shape[2:4], mode="bilinear", align_corners=True), skip], dim=1)
-        x = layer(x)
+    # the UNet (hand_teacher_mvp.py:444-467): the reference's lines at "fp32"; admitted levels on gol_conv3ub_* at "bf16x3"
+    x = olatunet.forward(self, x, joint_feat, precision=getattr(self, olatunet.UNET_PRECISION_FLAG, "fp32"))
     use_shadow = self.training and iteration is not None and iteration < 1000
     rgb, texolat, primshadow = olat.combine(x.to(torch.float32).contiguous(), light_intensity, shadow, self.primsize,
                                             self.n_prim_x, self.n_prim_y, use_shadow, self.training)

@@ -808,6 +808,57 @@ int gol_conv4x_bwd_w(int B, int Ci, int Co, int H, int W, const float* x, const 
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * gol_conv3ub_*: a 3x3 / stride 1 / zero padding 1 convolution of the channel concatenation of TWO tensors + untied bias +
+ * LeakyReLU at precision "bf16x3" (the split product of gol_conv3x_*, on v_mfma_f32_16x16x32_bf16) with forward and all four
+ * gradients: one level of the UNet of the MVP teacher on its EFFECTIVE weight.  Replaces, in OLATRGBDecoder.forward_rgb
+ * (ca_code/models/hand_teacher_mvp.py:444-467; layers built at :206-241 from nn.Sequential(la.Conv2dWNUB(n_in, n_out,
+ * kernel_size=3, height, width, stride=1, padding=1), nn.LeakyReLU(0.2, inplace=True)), ca_code/nn/layers.py),
+ *   x = th.cat([x, x_prev], dim=1)        (:460 with joint_feat, :466 with the skip; absent in the encoder)
+ *   x = layer(x)                          (:447, :467: F.conv2d + bias[None] + leaky_relu_)
+ * and, backward, the activation's, the bias add's, both convolution gradients' and the concatenation's kernels:
+ *   xcat = cat(xa [B,Ca,H,W], xb [B,Cb,H,W]) along channels, Ci = Ca + Cb; never written.  Cb == 0: xb is not read.
+ *   pre[b,co,r,c]  = sum_{ci,ky,kx} xcat_pad[b,ci,r-1+ky,c-1+kx] w[co,ci,ky,kx] + bias[co,r,c]     bias [Co,H,W]
+ *   y              = pre > 0 ? pre : leak pre                                                      y [B,Co,H,W], leak > 0
+ *   g_pre          = y > 0 ? g_y : leak g_y      (from the SAVED y: the activation is in place; at y == 0: leak, as torch)
+ *   g_xa, g_xb     = rows [0,Ca) and [Ca,Ci) of sum_{co,ky,kx} g_pre[b,co,r+1-ky,c+1-kx] w[co,ci,ky,kx]
+ *   g_w[co,ci,ky,kx] = sum_{b,r,c} g_pre[b,co,r,c] xcat_pad[b,ci,r-1+ky,c-1+kx]                    g_w [Co,Ci,3,3]
+ *   g_bias[co,r,c] = sum_b g_pre[b,co,r,c]                                                         fp32, b ascending
+ *   Every product a b of the three convolutions is lo_a hi_b + hi_a lo_b + hi_a hi_b with split(v): hi = bf16_rne(v),
+ *   lo = bf16_rne(v - float(hi)); BOTH operands are split (x and g_pre while they are staged, g_pre AFTER it is formed);
+ *   products are exact, the sum is fp32, lo lo is dropped: |result - exact| <= 3.1 2^-16 sum |a||b|.  Zero padding splits
+ *   to (0, 0).  Inputs finite and of ordinary magnitude, as for gol_conv3x_*.
+ * gol_conv3ub_pack splits w ONCE per call into packed[gol_conv3ub_packed_elems(Co, Ci)] (16-bit elements, 16-byte aligned):
+ *   [hi | lo][tap][Co / 8][Cip / 8][8 co][8 ci] with Cip = Ci rounded up to a multiple of 32 and zeros for the channels
+ *   past Ci; the same buffer serves fwd and bwd_x (which transposes a block on its way to LDS and mirrors the taps).
+ *   gol_conv3ub_packed_elems = 2 x 9 x Co x Cip, or 0 for an unsupported (Co, Ci).
+ * gol_conv3ub_bwd_x: g_xa [B,Ca,H,W] and g_xb [B,Cb,H,W] written; only rows < Ci are written; a NULL g_xa or g_xb skips
+ *   that tensor's rows (both NULL: no launch).
+ * gol_conv3ub_bwd_w: reads the fp32 xa, xb, y and g_y; K (the pixels) is split over workgroups, whose partials go to
+ *   scratch[gol_conv3ub_bwd_w_scratch_floats] and are added in block order by a second kernel (no float atomics).  The
+ *   scratch is blocks x 9 Co Ci floats with blocks = about 512 / ((Cip / 32) ceil(Co / 64)), at most one per 32 pixels of
+ *   a row: never more than (512 + (Cip / 32) ceil(Co / 64)) x 18432 floats, whatever B, H and W.  g_w == NULL: no launch.
+ * gol_conv3ub_bwd_bias: one streaming pass over y and g_y.  g_bias == NULL: no launch.
+ * Supported: Co % 32 == 0; Ca > 0, Ca % 8 == 0, Cb % 8 == 0, and Ca % 32 == 0 whenever Cb > 0 (a K stage of 32 channels
+ * reads one source); Ci need NOT be a multiple of 32 (the loaders supply zeros for the channels past Ci and read nothing
+ * for them); any H, W >= 1; B <= 65535 (gol_conv3ub_pack: Co % 32 == 0, Ci % 8 == 0; gol_conv3ub_bwd_bias: Co % 32 == 0).
+ * Everything else returns GOL_ERR_UNSUPPORTED before any launch (gol_conv3ub_bwd_w_scratch_floats: 0).  A null pointer
+ * that is needed, B < 0 or leak <= 0 returns GOL_ERR_INVALID_ARG; B == 0 returns GOL_OK without a kernel (bwd_w and
+ * bwd_bias zero their outputs).  Offsets are 64-bit across planes.  Every output element is a fixed-order sum: bitwise
+ * reproducible.  No host sync, no allocation: capturable as a linear graph.
+ * ---------------------------------------------------------------------------------------- */
+long long gol_conv3ub_packed_elems(int Co, int Ci);
+int gol_conv3ub_pack(int Co, int Ci, const float* weight, unsigned short* packed, void* stream);
+int gol_conv3ub_fwd(int B, int Ca, int Cb, int Co, int H, int W, float leak, const float* xa, const float* xb,
+                    const unsigned short* packed, const float* bias, float* y, void* stream);
+int gol_conv3ub_bwd_x(int B, int Ca, int Cb, int Co, int H, int W, float leak, const unsigned short* packed, const float* y,
+                      const float* g_y, float* g_xa, float* g_xb, void* stream);
+long long gol_conv3ub_bwd_w_scratch_floats(int B, int Ca, int Cb, int Co, int H, int W);
+int gol_conv3ub_bwd_w(int B, int Ca, int Cb, int Co, int H, int W, float leak, const float* xa, const float* xb,
+                      const float* y, const float* g_y, float* g_w, float* scratch, void* stream);
+int gol_conv3ub_bwd_bias(int B, int Co, int H, int W, float leak, const float* y, const float* g_y, float* g_bias,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * gol_mbconv_front_fwd / gol_mbconv_front_bwd_x: the front of an MBConv block of the frozen EfficientNet-B0 feature
  * network of the `effnet` / `effnet_phys` losses (ca_code/loss/effnet.py:45-51 runs torchvision's
  * efficientnet_b0().features[0:4]; registered at ca_code/loss/perceptual.py:60-69): expand 1x1 + BN + SiLU, depthwise
