@@ -74,4 +74,47 @@ __device__ __forceinline__ Terms terms(const Lobe& o, float c, float cc, float d
   return t;
 }
 
+// ---- the lobe angle without acos' conditioning (w_type 0 / 1) ---------------------------------------------------------
+// The angle between the direction d to a light (any length) and the unit lobe axis l as atan2(|d x l|, d . l): acos of the
+// clamped cosine for a unit l, but with an absolute error of a few ulps of 1 where acos(c) turns the rounding of c into
+// ulp / sin(angle) -- the sharp lobes (sigma ~ 0.01) live at angles of a few hundredths.  sin = |d x l| / |d| likewise
+// replaces sqrt(1 - c^2) in d acos / d c.  An axis that is not a unit vector (a zero reflection) keeps acos(0).
+struct Angle { float angle, sin; };
+
+__device__ __forceinline__ Angle angle_to(float dx, float dy, float dz, float lx, float ly, float lz, float inv_len) {
+  const float cx = dy * lz - dz * ly, cy = dz * lx - dx * lz, cz = dx * ly - dy * lx;
+  const float s = sqrtf(cx * cx + cy * cy + cz * cz), dot = dx * lx + dy * ly + dz * lz;
+  Angle a;
+  a.angle = (s == 0.f && dot == 0.f) ? 1.57079632679f : atan2f(s, dot);
+  a.sin = s * inv_len;
+  return a;
+}
+
+template <int W_TYPE>
+__device__ __forceinline__ float weight_at(const Lobe& o, float angle) {
+  static_assert(W_TYPE == 0 || W_TYPE == 1, "angle form: the acos lobes");
+  const float ex = __expf(-0.5f * sqr(angle * o.inv_sigma));
+  return W_TYPE == 0 ? ex * o.norm : ex;
+}
+
+// terms<W_TYPE> on that angle; the constant -20 of sg.cu:129,139 where the two directions are exactly (anti)parallel
+template <int W_TYPE>
+__device__ __forceinline__ Terms terms_at(const Lobe& o, const Angle& a, float dw) {
+  static_assert(W_TYPE == 0 || W_TYPE == 1, "angle form: the acos lobes");
+  Terms t;
+  const float angle = a.angle;
+  const float ex = __expf(-0.5f * sqr(angle * o.inv_sigma));
+  const float dacos = a.sin > 0.f ? -1.f / a.sin : -20.f;
+  if (W_TYPE == 0) {
+    t.weight = ex * o.norm;
+    t.gs = dw * ((ex * kInvSqrt2Pi23 * (sqr(angle) - o.s2)) * o.inv_s4);
+    t.dc = dw * -((kInvSqrt2Pi23 * angle * ex) * o.inv_s3) * dacos;
+  } else {
+    t.weight = ex;
+    t.gs = dw * ((ex * sqr(angle)) * o.inv_s3);
+    t.dc = dw * -((angle * ex) * o.inv_s2) * dacos;
+  }
+  return t;
+}
+
 }  // namespace gol_sg

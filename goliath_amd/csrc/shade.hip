@@ -291,9 +291,33 @@ __device__ __forceinline__ void env_rotate(const float* __restrict__ R, const fl
   ry = R[3] * ref[0] + R[4] * ref[1] + R[5] * ref[2];
   rz = R[6] * ref[0] + R[7] * ref[1] + R[8] * ref[2];
 }
-__device__ __forceinline__ EnvDir env_dir(const float* __restrict__ R, const float (&ref)[3]) {
+// The same direction from the planes themselves, in double.  Near a pole r_x and r_z are differences of O(1) terms: carried
+// in float (position - camera, the two normalisations, the reflection, the rotation) they keep an absolute error of a few
+// 1e-7, i.e. a relative error of 1e-7 / sin(polar angle) in the azimuth and in d u / d r -- 1e-4 a few mrad from the pole,
+// the whole error of the lookup and of its gradient there.  ~60 double operations per Gaussian on a stage that waits for HBM.
+__device__ __forceinline__ void env_rotate_precise(const float* __restrict__ R, const float (&g)[12], const float (&fc)[4],
+                                                   const float (&pb)[3], const float (&nb)[3], const float* __restrict__ cam,
+                                                   float& rx, float& ry, float& rz) {
+  double d[3], m[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    d[k] = ((double)g[k] + (double)pb[k]) - (double)cam[k];
+    m[k] = (double)fc[1 + k] + (double)nb[k];
+  }
+  const double id = 1.0 / fmax(sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]), (double)kNormEps);
+  const double im = 1.0 / fmax(sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]), (double)kNormEps);
+  const double vdn = (d[0] * m[0] + d[1] * m[1] + d[2] * m[2]) * (id * im);
+  double ref[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) ref[k] = d[k] * id - 2.0 * vdn * (m[k] * im);
+  rx = (float)((double)R[0] * ref[0] + (double)R[1] * ref[1] + (double)R[2] * ref[2]);
+  ry = (float)((double)R[3] * ref[0] + (double)R[4] * ref[1] + (double)R[5] * ref[2]);
+  rz = (float)((double)R[6] * ref[0] + (double)R[7] * ref[1] + (double)R[8] * ref[2]);
+}
+__device__ __forceinline__ EnvDir env_dir(const float* __restrict__ R, const float (&g)[12], const float (&fc)[4],
+                                          const float (&pb)[3], const float (&nb)[3], const float* __restrict__ cam) {
   EnvDir d;
-  env_rotate(R, ref, d.rx, d.ry, d.rz);
+  env_rotate_precise(R, g, fc, pb, nb, cam, d.rx, d.ry, d.rz);
   d.u = atan2f(d.rx, d.rz) * (1.f / kPi);
   // polar angle = acos(r_y) (envmap.py:289) evaluated as atan2(sqrt(r_x^2 + r_z^2), r_y): the same angle for a unit vector,
   // without acos' loss of the rounding of r_y near the poles (acos'(y) = -1 / sqrt(1 - y^2) amplifies it without bound).
@@ -305,10 +329,11 @@ __device__ __forceinline__ EnvDir env_dir(const float* __restrict__ R, const flo
 
 // specular radiance before the spec_vis factor; ENV: min(sample, 1) (rgca.py:556)
 template <bool ENV>
-__device__ __forceinline__ void spec_forward(const gol_shade_in& in, int b, const Geo& s, float (&spec)[3],
-                                             EnvSample* keep = nullptr) {
+__device__ __forceinline__ void spec_forward(const gol_shade_in& in, int b, const Geo& s, const float (&g)[12],
+                                             const float (&fc)[4], const float (&pb)[3], const float (&nb)[3],
+                                             float (&spec)[3], EnvSample* keep = nullptr) {
   if constexpr (ENV) {
-    const EnvDir d = env_dir(in.lightrot + 9 * b, s.ref);
+    const EnvDir d = env_dir(in.lightrot + 9 * b, g, fc, pb, nb, in.campos + 3 * b);
     const EnvSample e = env_lookup(in, b, d.u, d.v, 5.f * s.sigma);
     if (keep) *keep = e;
 #pragma unroll
@@ -324,9 +349,8 @@ __device__ __forceinline__ void spec_forward(const gol_shade_in& in, int b, cons
     spec[0] = spec[1] = spec[2] = 0.f;
     for (int l = 0; l < nL; ++l) {
       const float dx = lp[3 * l] - s.pos[0], dy = lp[3 * l + 1] - s.pos[1], dz = lp[3 * l + 2] - s.pos[2];
-      const float r = rsqrtf(dx * dx + dy * dy + dz * dz);
-      const float c = fminf(1.f, fmaxf(-1.f, (dx * lx + dy * ly + dz * lz) * r));
-      const float w = gol_sg::weight<0>(lobe, c);
+      // the angle as atan2(|d x l|, d . l), not acos of the cosine (gol_sg_lobe.h: the sharp lobes' conditioning)
+      const float w = gol_sg::weight_at<0>(lobe, gol_sg::angle_to(dx, dy, dz, lx, ly, lz, 0.f).angle);
       spec[0] += lv[3 * l] * w; spec[1] += lv[3 * l + 1] * w; spec[2] += lv[3 * l + 2] * w;
     }
   }
@@ -371,7 +395,7 @@ __global__ __launch_bounds__(256, 4) void shade_fwd_kernel(const gol_shade_in in
     const Geo s = make_geo(x.g, x.fc, x.pb, x.nb, in.campos + 3 * b);
     float spec[3];
     EnvSample es;
-    spec_forward<ENV>(in, b, s, spec, ENV ? &es : nullptr);
+    spec_forward<ENV>(in, b, s, x.g, x.fc, x.pb, x.nb, spec, ENV ? &es : nullptr);
     float o_sc[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -485,11 +509,15 @@ __global__ __launch_bounds__(256, 4) void shade_fwd_kernel(const gol_shade_in in
   p = out.diff_color + g0 * 3; p[0] = diff[0]; p[1] = diff[1]; p[2] = diff[2];
   p = out.diff_sum + g0 * 3; p[0] = Ds[0]; p[1] = Ds[1]; p[2] = Ds[2];
   if (RAND) {
+    // color_rand = clamp(sum, min=0) (rgca.py:616), whose gradient passes where sum >= 0, the tie included.  The backward
+    // re-reads only this output, so a clamped element is stored as -0.0f: the same value, and its sign bit is the mask
     p = out.color_rand + g0 * 3;
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
-      p[c] = fmaxf((s_D[0][3 + c][threadIdx.x] + s_D[1][3 + c][threadIdx.x]) +
-                   (s_D[2][3 + c][threadIdx.x] + s_D[3][3 + c][threadIdx.x]), 0.f);
+    for (int c = 0; c < 3; ++c) {
+      const float sum = (s_D[0][3 + c][threadIdx.x] + s_D[1][3 + c][threadIdx.x]) +
+                        (s_D[2][3 + c][threadIdx.x] + s_D[3][3 + c][threadIdx.x]);
+      p[c] = sum < 0.f ? -0.f : fabsf(sum);  // fabsf: a sum of -0.0f is not below zero and must not read as clamped
+    }
   }
   if constexpr (PROJ)
     gol_record_write(pj.records + g0 * GOL_SPLAT_RECORD, c_rec[0], c_rec[1], c_rec[2], c_rec[3], c_rec[4], c_rec[5],
@@ -545,6 +573,20 @@ __global__ __launch_bounds__(256, 3) void shade_bwd_kernel(const gol_shade_in in
     ld_aos<V, 3>(in.albedo, (size_t)i0, alb);
     ld_aos<V, 3>(saved.diff_sum, g0, Dsum);
     if (RAND) ld_aos<V, 3>(saved.color_rand, g0, crand);
+
+    // the env direction first, while nothing but the planes is live: its double temporaries would otherwise sit on top of
+    // the 37 upstream gradients and spill (the kernel is at its 168-VGPR bound)
+    float erx = 0.f, ery = 0.f, erz = 0.f;
+    if constexpr (ENV) {
+      float g1[12], f1[4], p3[3], n3[3];
+#pragma unroll
+      for (int j = 0; j < 12; ++j) g1[j] = g[j][0];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f1[j] = fc[j][0];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) { p3[j] = pb[j][0]; n3[j] = nb[j][0]; }
+      env_rotate_precise(in.lightrot + 9 * b, g1, f1, p3, n3, in.campos + 3 * b, erx, ery, erz);
+    }
 
     float u_color[3][V], u_op[1][V], u_pos[3][V], u_q[4][V], u_sc[3][V], u_sp[3][V], u_sig[1][V], u_vis[1][V];
     float u_n[3][V], u_dn[3][V], u_diff[3][V], u_spec[3][V], u_nb[3][V], u_rand[3][V];
@@ -613,7 +655,7 @@ __global__ __launch_bounds__(256, 3) void shade_bwd_kernel(const gol_shade_in in
           have_env = true;
         }
       }
-      if (!have_env) spec_forward<ENV>(in, b, s, spec, ENV ? &e : nullptr);
+      if (!have_env) spec_forward<ENV>(in, b, s, g1, f1, p3, n3, spec, ENV ? &e : nullptr);
 
       // colour composition (rgca.py:572-575): color_out = max(max(diff,0) + spec*vis, 0)
       float g_spec[3], g_sraw[3], g_vis = u_vis[0][v];
@@ -628,7 +670,7 @@ __global__ __launch_bounds__(256, 3) void shade_bwd_kernel(const gol_shade_in in
         g_sraw[c] = g_spec[c] * s.vis;
         gD[c][v] = g_diff * alb[c][v];
         galb[c][v] = g_diff * Dsum[c][v];
-        gDr[c][v] = RAND ? ((crand[c][v] > 0.f) ? u_rand[c][v] : 0.f) : 0.f;
+        gDr[c][v] = RAND ? (!signbit(crand[c][v]) ? u_rand[c][v] : 0.f) : 0.f;  // -0.0f = clamped (see the forward)
       }
       gfc[0][v] = g_vis * s.vis * (1.f - s.vis);
 
@@ -636,8 +678,7 @@ __global__ __launch_bounds__(256, 3) void shade_bwd_kernel(const gol_shade_in in
       float g_ref[3] = {0.f, 0.f, 0.f}, g_sigma = u_sig[0][v];
       if constexpr (ENV) {
         const float* R = in.lightrot + 9 * b;
-        float rx, ry, rz;  // the direction alone: a struct with the two unused angles cost <1,1,1,0> 12 B of scratch
-        env_rotate(R, s.ref, rx, ry, rz);
+        const float rx = erx, ry = ery, rz = erz;  // (computed at the top of the phase)
         float g_u = 0.f, g_v = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -667,11 +708,10 @@ __global__ __launch_bounds__(256, 3) void shade_bwd_kernel(const gol_shade_in in
         for (int l = 0; l < nL; ++l) {
           float dx = lp[3 * l] - s.pos[0], dy = lp[3 * l + 1] - s.pos[1], dz = lp[3 * l + 2] - s.pos[2];
           const float r = rsqrtf(dx * dx + dy * dy + dz * dz);
+          const gol_sg::Angle ang = gol_sg::angle_to(dx, dy, dz, lx, ly, lz, r);
           dx *= r; dy *= r; dz *= r;
-          const float c = dx * lx + dy * ly + dz * lz;
-          const float cc = fminf(1.f, fmaxf(-1.f, c));
           const float dw = g_sraw[0] * lv[3 * l] + g_sraw[1] * lv[3 * l + 1] + g_sraw[2] * lv[3 * l + 2];
-          const gol_sg::Terms t = gol_sg::terms<0>(lobe, c, cc, dw);
+          const gol_sg::Terms t = gol_sg::terms_at<0>(lobe, ang, dw);
           const float dc = t.dc;
           gs += t.gs;
           gx += dc * dx; gy += dc * dy; gz += dc * dz;

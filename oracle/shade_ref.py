@@ -52,8 +52,9 @@ def mip_sample(mips, uv, level):
 
 def shade(f_vnocond, f_vcond, postex, tn, albedo, light_sh, campos, light_intensity=None,
           light_pos=None, n_lights=None, envmips=None, lightrot=None, light_sh_rand=None,
-          n_color_sh=3, n_diff_sh=8, sg_eval=None):
+          n_color_sh=3, n_diff_sh=8, sg_eval=None, coefs=None):
     """Returns the dict of rgca.py:574-588 (+ color_rand when light_sh_rand is given).
+    coefs=(ncol, nmono) overrides the coefficient counts derived from the two SH degrees (shade.shading_tail_coefs).
 
     f_vnocond[B,3*(n_color_sh+1)^2 + ((n_diff_sh+1)^2-(n_color_sh+1)^2) + 12, S, S], f_vcond[B,4,S,S],
     postex[B,3,S,S] (uv position map), tn[B,3,S,S] (normalised uv normal map), albedo[1,N,3],
@@ -62,13 +63,15 @@ def shade(f_vnocond, f_vcond, postex, tn, albedo, light_sh, campos, light_intens
     B = f_vnocond.shape[0]
     ncol = (n_color_sh + 1) ** 2
     nmono = (n_diff_sh + 1) ** 2 - ncol
+    if coefs is not None:
+        ncol, nmono = coefs
     nd = 3 * ncol + nmono
     flat = lambda t: t.reshape(B, t.shape[1], -1).permute(0, 2, 1)  # [B,C,S,S] -> [B,N,C]
     fv, fc = flat(f_vnocond), flat(f_vcond)
     posbase, nmlbase = flat(postex), flat(tn)
 
-    sh_col = fv[..., : 3 * ncol].reshape(B, -1, 3, ncol)
-    sh_mono = fv[..., 3 * ncol: nd].reshape(B, -1, 1, nmono)
+    sh_col = fv[..., : 3 * ncol].reshape(B, fv.shape[1], 3, ncol)
+    sh_mono = fv[..., 3 * ncol: nd].reshape(B, fv.shape[1], 1, nmono)   # (no -1: nmono may be 0)
     sh_all = torch.cat([sh_col, sh_mono.expand(-1, -1, 3, -1)], -1)  # rgca.py:506-514
     geo = fv[..., nd: nd + 11]
     primpos = geo[..., 0:3] + posbase
