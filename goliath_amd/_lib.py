@@ -52,6 +52,8 @@ _SYMBOLS = [
     "gol_conv4x_bwd_w",
     "gol_conv3ub_packed_elems", "gol_conv3ub_pack", "gol_conv3ub_fwd", "gol_conv3ub_bwd_x",
     "gol_conv3ub_bwd_w_scratch_floats", "gol_conv3ub_bwd_w", "gol_conv3ub_bwd_bias",
+    "gol_upconvx_packed_elems", "gol_upconvx_pack", "gol_upconvx_fwd", "gol_upconvx_bwd_x",
+    "gol_upconvx_bwd_w_scratch_floats", "gol_upconvx_bwd_w", "gol_upconvx_bwd_gate",
     "gol_mbconv_front_tiles", "gol_mbconv_front_fwd", "gol_mbconv_front_bwd_x",
 ]
 

@@ -1,8 +1,8 @@
 // gol_upconv.h -- what upconv.hip (bilinear 2x + conv3) and upcat.hip (leaky + bilinear 2x + concat + conv3) compile
-// identically: the coordinate tables of the integer-ratio rule, the blending loader, the 3x3 MFMA core and the fixed-order
+// identically: the coordinate tables of the integer-ratio rule (gol_upcoord.h), the blending loader, the 3x3 MFMA core and the fixed-order
 // reduction of the weight gradient's partial sums.  Everything lives in an unnamed namespace: a copy per translation unit.
 #pragma once
-#include "gol_common.h"
+#include "gol_upcoord.h"  // the coordinate rule: up_fill_axis, up_first_row, up_blend
 
 namespace {
 
@@ -20,33 +20,6 @@ constexpr int kUR = 12, kUC = 36;             // the region of g_U that reaches 
 constexpr int kGR = kUR + 2, kGC = kUC + 2;   // haloed window of g_pre
 constexpr int kBxPlane = 592;                 // >= 14 * 38, == 16 (mod 64)
 constexpr int kBxNPT = 7;                     // pixel tiles of 16 per wave: 4 x 7 x 16 >= 12 x 36 = 27 x 16
-
-// ---- the coordinate rule ---------------------------------------------------------------------------------------------
-// Tables of n rows (or columns) origin .. origin + n - 1 of U: source offsets a = r0 * mul, b = r1 * mul and the fraction;
-// a = -1 marks a row outside [0, nout).
-__device__ __forceinline__ void up_fill_axis(int* s_a, int* s_b, float* s_f, int n, int origin, int nsrc, int nout, int mul,
-                                             int tid) {
-  for (int t = tid; t < n; t += 256) {
-    const int r = origin + t;
-    int a = -1, b = 0;
-    float f = 0.f;
-    if (r >= 0 && r < nout) {
-      const int nr = r * (nsrc - 1), d = nout - 1;  // (nout = 2 nsrc >= 2)
-      const int q = nr / d;
-      f = (float)(nr - q * d) / (float)d;
-      a = q * mul;
-      b = min(q + 1, nsrc - 1) * mul;
-    }
-    s_a[t] = a;
-    s_b[t] = b;
-    s_f[t] = f;
-  }
-}
-
-// first row of U with r (nsrc-1)/(nout-1) > i - 1: no earlier row reaches source row i
-__device__ __forceinline__ int up_first_row(int i, int nsrc, int nout) {
-  return (i <= 0 || nsrc <= 1) ? 0 : ((i - 1) * (nout - 1)) / (nsrc - 1) + 1;
-}
 
 // KC planes of the ROWS x COLS window of U into LDS, blended from x; outside the image and past Ci: zeros.
 // LEAKY: the texels go through x > 0 ? x : leak x before the blend (upcat.hip: the previous layer's activation).

@@ -625,7 +625,8 @@ def patch_image_ops(*modules):
 
 
 def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, texture_decoder=False, texture_tail=False,
-                 displacement_unet=False, feat_encoder=False, feat_encoder_precision="fp32"):
+                 displacement_unet=False, feat_encoder=False, feat_encoder_precision="fp32",
+                 texture_decoder_precision="fp32"):
     """BASELINE config 4 as a drop-in: `ConvTeacherDecoder.forward` (ca_code/models/urhand.py:349-630) with its two light
     loops and both shadow-map evaluations on the HIP kernels (goliath_amd.urhand.conv_teacher_decoder_forward) and the
     stand-alone shadow-map lookup (`get_shadow_map`, imported at urhand.py:44).  The depth images of the light cameras are
@@ -655,6 +656,12 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, t
     the reference's three lines everywhere else (plain nn.Conv2d layers, CPU tensors, inputs that are not half the target
     size, shapes that lost the probe).  Opt-in: the default binding clears the flag and is unchanged.  The measured gain per
     layer shape is written by tools/texdec_probe.py to profiles/texdec_probe.json.
+    texture_decoder_precision ("fp32" by default, or "bf16x3") is stored next to the flag as
+    `texdec.TEXDEC_PRECISION_FLAG` and handed to texture_branches: at "bf16x3" a recognised layer whose shape passes
+    texdec.supported_bf16x3 and is in texdec.DISPATCH_BF16X3 runs on the split-bf16 operator (gol_upconvx_*: the same
+    fusion on three bf16 MFMAs per product; tools/texdecx_probe.py, profiles/texdecx_probe.json, DESIGN.md section
+    6c-sexies); every other layer takes exactly the decision above.  It has no effect without texture_decoder=True; an
+    unknown value raises ValueError.
 
     texture_tail=True rebinds `AutoEncoder.forward` (urhand.py:750-990) to goliath_amd.urhand.autoencoder_forward -- the same
     parameter list, the same `preds` keys -- and sets `uvtex.TEXTURE_TAIL_FLAG` on the class: the stretch from the decoder's
@@ -715,6 +722,7 @@ def patch_urhand(urhand_module=None, mesh_render_layer=False, uv_frames=False, t
     urhand_module.ConvTeacherDecoder.forward = (urhand.conv_teacher_decoder_forward_uv_frames if uv_frames
                                                 else urhand.conv_teacher_decoder_forward)
     setattr(urhand_module.ConvTeacherDecoder, texdec.TEXTURE_DECODER_FLAG, bool(texture_decoder))
+    setattr(urhand_module.ConvTeacherDecoder, texdec.TEXDEC_PRECISION_FLAG, texdec._precision(texture_decoder_precision))
     setattr(urhand_module.ConvTeacherDecoder, dispunet.DISPLACEMENT_UNET_FLAG, bool(displacement_unet))
     setattr(urhand_module.ConvTeacherDecoder, featenc.FEATENC_FLAG, bool(feat_encoder))
     setattr(urhand_module.ConvTeacherDecoder, featenc.FEATENC_PRECISION_FLAG, featenc._precision(feat_encoder_precision))

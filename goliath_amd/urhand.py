@@ -14,6 +14,7 @@
     either forward, where the decoder class carries texdec.TEXTURE_DECODER_FLAG (dropin.patch_urhand(texture_decoder=True)):
         * the two 7-layer texture branches (:583-608): 2x bilinear resize + weight-normalised 3x3 conv + bias / LeakyReLU
           or gate / gainbias per layer               -> gol_upconv_fwd/bwd (goliath_amd.texdec), per shape, opt-in
+          with texture_decoder_precision="bf16x3"    -> gol_upconvx_* (split-bf16 MFMA), per shape, opt-in
     either forward, where the decoder class carries dispunet.DISPLACEMENT_UNET_FLAG (dropin.patch_urhand(displacement_unet=True)):
         * the decoder levels of the displacement / roughness UNet (:217-226, :231-239): leaky + 2x bilinear resize + concat +
           weight-normalised 3x3 conv (+ tanh head)     -> gol_upcat_conv_fwd/bwd (goliath_amd.dispunet), per shape, opt-in
@@ -238,7 +239,8 @@ def _decoder_forward(self, fused_frames, lbs_motion, id_mesh, tex_mean, verts_re
     else:
         z, gainbias = self.featenc(feat_in)
     if getattr(type(self), texdec.TEXTURE_DECODER_FLAG, False):   # dropin.patch_urhand(texture_decoder=True)
-        x = texdec.texture_branches(self, joint_feat, z, gainbias)
+        x = texdec.texture_branches(self, joint_feat, z, gainbias,
+                                    precision=getattr(type(self), texdec.TEXDEC_PRECISION_FLAG, "fp32"))
     else:
         acts, x, hh = [], joint_feat, 64
         for i in range(self.n_layers_tex):               # non-linear branch

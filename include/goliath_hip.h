@@ -859,6 +859,57 @@ int gol_conv3ub_bwd_bias(int B, int Co, int H, int W, float leak, const float* y
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * gol_upconvx_*: the texture-decoder layer of gol_upconv_* above at precision "bf16x3".  Replaces the same lines of
+ * ConvTeacherDecoder.forward (ca_code/models/urhand.py:583-608; layers built at :302-323): F.interpolate(x, (2 Hi, 2 Wi),
+ * mode="bilinear", align_corners=True), the MIOpen convolution and the epilogue of texmod0 (:592-597) or texmod1 (:600-606),
+ * and their backward kernels.  The formulas are gol_upconv_*'s, with the same integer-ratio coordinate rule and the same modes:
+ *   U[b,ci,r,c]   = bilinear(x[b,ci]) by the integer-ratio rule, blended in fp32          (H = 2 Hi, W = 2 Wi; never written)
+ *   acc[b,co,r,c] = sum_{ci,ky,kx} Upad[b,ci,r-1+ky,c-1+kx] w[co,ci,ky,kx]
+ *   mode 0:  y = lrelu(acc + bias[co,r,c], leak), leak > 0       mode 1:  y = (acc * gate + gb) * scale   (gb may be NULL)
+ *   g_pre = g_y * (y > 0 ? 1 : leak) (mode 0; needs y) or scale * gate * g_y (mode 1; needs gate), formed in fp32
+ *   g_x = bilinear adjoint of sum_{co,ky,kx} g_pre[b,co,r+1-ky,c+1-kx] w[co,ci,ky,kx];  g_w = sum_{b,r,c} g_pre Upad
+ *   g_gate = scale * g_y * acc (acc recomputed), g_gb = scale * g_y
+ *   The only difference: every product a b of the three convolutions is lo_a hi_b + hi_a lo_b + hi_a hi_b with split(v):
+ *   hi = bf16_rne(v), lo = bf16_rne(v - float(hi)); BOTH operands are split while they are staged (U AFTER the fp32 blend,
+ *   g_pre AFTER it is formed); products are exact, the sum is fp32, lo lo is dropped: |result - exact| <= 3.1 2^-16
+ *   sum |a||b|.  Padding splits to (0, 0).  Inputs finite and of ordinary magnitude, as for gol_conv3x_*.
+ * gol_upconvx_pack splits w_eff [Co,Ci,3,3] ONCE per call into packed[gol_upconvx_packed_elems(Co, Ci)] (16-bit elements,
+ *   16-byte aligned): [hi | lo][tap][Cop / 8][Ci / 8][8 co][8 ci] with Cop = Co rounded up to a multiple of 32 and zeros for
+ *   the rows past Co (gol_conv3ub_pack's layout padded on the Co side; that entry is not reused because its channel rule,
+ *   Co % 32 == 0, is pinned by its tests).  The same buffer serves fwd, bwd_x (which transposes a block on its way to LDS and
+ *   mirrors the taps) and bwd_gate.  gol_upconvx_packed_elems = 2 x 9 x Cop x Ci, or 0 for an unsupported (Co, Ci).
+ * gol_upconvx_fwd: x [B,Ci,Hi,Wi]; bias [Co,H,W] (mode 0); gate, gb, y [B,Co,H,W].  Nothing but y is written.
+ * gol_upconvx_bwd_x: g_x [B,Ci,Hi,Wi] written; per tile of 2 x 14 texels the region of g_U that reaches it (8 x 32 pixels)
+ *   is kept on chip and every texel gathers its up-to-5x5 pixels in fp32 (no atomics).  g_x == NULL: no launch.
+ * gol_upconvx_bwd_w: g_w [Co,Ci,3,3] written; reads the fp32 x, y or gate, and g_y (U recomputed).  K (the pixels, in chunks
+ *   of 32 of an output row) is split over workgroups, whose partials go to scratch[gol_upconvx_bwd_w_scratch_floats] and are
+ *   added in block order by a second kernel (no float atomics).  The scratch is blocks x 9 Co Ci floats with
+ *   blocks = min(ceil(512 / pairs), chunks) rounded so that no block is empty, pairs = (Ci / 32) ceil(Co / 64),
+ *   chunks = B H ceil(W / 32): never more than (512 + pairs) x 18432 floats, whatever B, Hi and Wi.  g_w == NULL: no launch.
+ * gol_upconvx_bwd_gate (mode 1): g_gate [B,Co,H,W] = scale * g_y * acc with acc recomputed by the forward kernel; g_gb (may
+ *   be NULL) rides along.  g_gate == NULL: no launch, and g_gb is NOT written.
+ * g_bias (mode 0) and g_gb without g_gate (mode 1) hold no product: they are gol_upconv_bwd's streaming pass, called with
+ *   every other output NULL.
+ * Supported: Ci % 32 == 0, Co % 16 == 0 (six of the seven layer shapes; 16 -> 4 stays on gol_upconv_*), Hi, Wi >= 1,
+ * B <= 65535; everything else returns GOL_ERR_UNSUPPORTED before any launch (the size queries: 0).  A negative size, a mode
+ * other than 0 / 1, leak <= 0 in mode 0 or a null pointer that is needed returns GOL_ERR_INVALID_ARG before any launch;
+ * B == 0 returns GOL_OK without a kernel (bwd_w zeroes g_w).  Offsets are 64-bit across planes.  Every output element is a
+ * fixed-order sum: bitwise reproducible.  No host sync, no allocation: capturable as a linear graph.
+ * ---------------------------------------------------------------------------------------- */
+long long gol_upconvx_packed_elems(int Co, int Ci);
+int gol_upconvx_pack(int Co, int Ci, const float* weight, unsigned short* packed, void* stream);
+int gol_upconvx_fwd(int B, int Ci, int Co, int Hi, int Wi, int mode, float leak, float scale, const float* x,
+                    const unsigned short* packed, const float* bias, const float* gate, const float* gb, float* y,
+                    void* stream);
+int gol_upconvx_bwd_x(int B, int Ci, int Co, int Hi, int Wi, int mode, float leak, float scale, const unsigned short* packed,
+                      const float* y, const float* gate, const float* g_y, float* g_x, void* stream);
+long long gol_upconvx_bwd_w_scratch_floats(int B, int Ci, int Co, int Hi, int Wi);
+int gol_upconvx_bwd_w(int B, int Ci, int Co, int Hi, int Wi, int mode, float leak, float scale, const float* x,
+                      const float* y, const float* gate, const float* g_y, float* g_w, float* scratch, void* stream);
+int gol_upconvx_bwd_gate(int B, int Ci, int Co, int Hi, int Wi, float scale, const float* x, const unsigned short* packed,
+                         const float* g_y, float* g_gate, float* g_gb, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * gol_mbconv_front_fwd / gol_mbconv_front_bwd_x: the front of an MBConv block of the frozen EfficientNet-B0 feature
  * network of the `effnet` / `effnet_phys` losses (ca_code/loss/effnet.py:45-51 runs torchvision's
  * efficientnet_b0().features[0:4]; registered at ca_code/loss/perceptual.py:60-69): expand 1x1 + BN + SiLU, depthwise
